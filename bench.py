@@ -17,6 +17,10 @@ contiguous bands -- with one RCCL all-to-all-v of the device-resident Fourier bu
 of the whole job.
 
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line (`--dump-outputs DIR` also writes the arrays of the last
+timed step).  `--full` adds the legs that take runs of their own, after the timed steps: the same loop on a dense spectrum, the
+host-array (PCIe-inclusive) rate, the CPU baselines and the Fortran host.
 """
 import argparse
 import json
@@ -411,6 +415,37 @@ def exchange_report(rs, world, nprtrw, nprtrv, steps):
     }
 
 
+DUMP_BYTES = 60_000_000  # --dump-outputs: all arrays together, .npy headers aside (limit 64 MB)
+DUMP_SEED = 20261016
+
+
+def dump_points(npts, fields_per_point, esz, budget, seed, keep=None):
+    """Indices along the point axis of one dumped array: every point if the array fits `budget` bytes, else a sorted sample
+    drawn by a generator seeded with `seed` (the same points for the same workload, run after run), always holding `keep`."""
+    n = min(npts, max(1, budget // max(fields_per_point * esz, 1)))
+    if n >= npts:
+        return np.arange(npts)
+    idx = np.random.default_rng(seed).choice(npts, n - (keep is not None), replace=False)
+    if keep is not None:
+        idx = np.union1d(idx, [keep])
+    return np.sort(idx)
+
+
+def dump_outputs(path, arrays, i419):
+    """--dump-outputs: `arrays` = [(name, device tensor, point axis)] as the timed path leaves them; each goes to path/<name>.npy
+    in its own dtype (float64 or float32), the point axis (spectral coefficients or grid points) cut to a fixed sample when the
+    whole set would pass DUMP_BYTES.  Spectral samples always hold the coefficient of the benchmark harmonic (m = 4, n = 19)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_BYTES // len(arrays)
+    for k, (name, a, axis) in enumerate(arrays):
+        npts = a.shape[axis]
+        idx = dump_points(npts, a.numel() // max(npts, 1), a.element_size(), budget, DUMP_SEED + k,
+                          keep=i419 if name.startswith("sp") else None)
+        sel = a if len(idx) == npts else a.index_select(axis, torch.as_tensor(idx, device=a.device))
+        np.save(os.path.join(path, name + ".npy"), sel.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -421,10 +456,16 @@ def main():
     ap.add_argument("--nfld", type=int, default=10)
     ap.add_argument("--precision", type=int, default=8, choices=(4, 8),
                     help="8: fp64 library (headline metric); 4: fp32 library (BASELINE configs[4]'s arithmetic)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle legs: cpu_baseline and the dense sub-record")
-    ap.add_argument("--no-api-level", action="store_true", help="skip the host-array (PCIe-inclusive) measurement")
-    ap.add_argument("--no-dense-timing", action="store_true", help="skip the second timed loop on the dense spectrum")
-    ap.add_argument("--no-fortran", action="store_true", help="skip the Fortran host leg (fortran_device_resident)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side legs after the timed steps: the dense-spectrum loop, the host-array rate, the CPU baselines "
+                         "and the Fortran host (each can be left out with its --no-* option); without it only the headline loop runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (grid-point and spectral arrays; a fixed, seeded sample of the "
+                         "points where an array is large, at most 64 MB in all) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the oracle legs: cpu_baseline and the dense sub-record")
+    ap.add_argument("--no-api-level", action="store_true", help="with --full: skip the host-array (PCIe-inclusive) measurement")
+    ap.add_argument("--no-dense-timing", action="store_true", help="with --full: skip the second timed loop on the dense spectrum")
+    ap.add_argument("--no-fortran", action="store_true", help="with --full: skip the Fortran host leg (fortran_device_resident)")
     ap.add_argument("--max-batch", type=int, default=0)
     ap.add_argument("--nprtrv", type=int, default=int(os.environ.get("EMI_BENCH_NPRTRV", "1")),
                     help="V-sets (N > 1 only): NPRTRW = N / NPRTRV; levels dealt to the V-sets as ectrans-benchmark.F90:329-344, 440-447")
@@ -605,13 +646,17 @@ def main():
     # ---- timed region: the reference harness's input (one harmonic), exactly K steps
     dt, step_ms, med_ms, (pack_ms, leg_ms, fft_ms), leg_launches, (xch_ms, xch_calls, xch_bytes), fft_kernels = timed_loop(args.steps)
     n1 = et.specnorm(r, spsc2, **({"kvset": kv["kvsetsc2"]} if kv else {}))[0]
+    if args.dump_outputs and rank == 0:
+        # before anything else reuses the arrays: inv_trans's grid-point fields and dir_trans's spectral fields of the last step
+        dump_outputs(args.dump_outputs, [("gpuv", gpuv, 3), ("gp3a", gp3a, 3), ("gp2", gp2, 2), ("spvor", spvor, 0),
+                                         ("spdiv", spdiv, 0), ("spsc3a", spsc3a, 1), ("spsc2", spsc2, 0)], i419)
 
     # ---- the same loop on a DENSE spectrum: every coefficient of every field ~ U(-0.5, 0.5) / (n + 1) from
     # a seed-20251114 generator, every field distinct, imag(m = 0) = 0, (0, 0) of vor / div = 0 -- filled on the device into the same
     # arrays.  99.9 % of the harmonic loop's Legendre products multiply zeros; this one shows whether the kernels (and the chip's
     # clock) care.  `value` stays the harmonic loop, the reference's metric (ectrans-benchmark.F90:1390-1415).
     dense_t = None
-    if not args.no_dense_timing:
+    if args.full and not args.no_dense_timing:
         nasm0_l = et.trans_inq(r, "nasm0")
         inv_np1 = np.zeros(nspec2)
         i00 = None
@@ -738,15 +783,15 @@ def main():
                 "roofline_frac": d_ach / (peak * world), "roofline_achieved_TFLOPs": d_ach,
                 "vs_harmonic_ms_per_step": d_ms / ms_step,
                 "spectral_norm_rel_error_round_trip": dense_t["drift"]}
-        if world == 1 and not args.no_api_level:
+        if world == 1 and args.full and not args.no_api_level:
             # free the device-resident benchmark arrays first: the staging buffers of the host calls need the room
             del spvor, spdiv, spsc3a, spsc2, gpuv, gp3a, gp2
             torch.cuda.empty_cache()
             out["api_level"] = api_level(et, r, N, kf, esz)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             torch.cuda.empty_cache()
             out["cpu_baseline"], out["dense"], out["cpu_baseline_blas"] = cpu_baseline(N, kf, gpu=(et, r, dev) if esz == 8 else None)
-        if world == 1 and esz == 8 and not args.no_fortran:
+        if world == 1 and esz == 8 and args.full and not args.no_fortran:
             # last leg: this process gives the GPU back (the Fortran host allocates the same 200 GB itself)
             try:
                 del spvor, spdiv, spsc3a, spsc2, gpuv, gp3a, gp2

@@ -60,3 +60,17 @@ def test_counter_files_are_quoted_only_for_the_running_build(tmp_path, monkeypat
     assert bench.recorded_fft_bound(1279, 137, 10, 4, 1, "abc")["fft_ms_per_pair_under_profiler"] == 101.0
     assert bench.recorded_fft_bound(1279, 137, 10, 8, 1, "zzz")["bound"] is None
     assert bench.recorded_fft_bound(399, 137, 4, 8, 1, "abc") is None
+
+
+def test_dump_sample_is_fixed_and_within_budget():
+    """--dump-outputs: the points of a large array are a seeded sample (the same ones run after run), within the byte budget, sorted,
+    holding the point asked for; a small array goes out whole."""
+    budget = bench.DUMP_BYTES // 7
+    a = bench.dump_points(1_640_000, 1370, 8, budget, 3, keep=12345)
+    b = bench.dump_points(1_640_000, 1370, 8, budget, 3, keep=12345)
+    assert np.array_equal(a, b) and 12345 in a and np.all(np.diff(a) > 0)
+    assert 0 < len(a) * 1370 * 8 <= budget
+    g = bench.dump_points(6_600_000, 1, 4, budget, 4)
+    assert len(g) == budget // 4 and np.all(np.diff(g) > 0) and g[-1] < 6_600_000
+    assert np.array_equal(bench.dump_points(1000, 20, 8, budget, 5), np.arange(1000))
+    assert 7 * budget <= 64e6

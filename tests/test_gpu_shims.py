@@ -254,6 +254,35 @@ def test_bench_multi_rank_launch(ngpus, nprtrv):
     assert out["fft_launches_per_direction"] >= 1
 
 
+def test_bench_plain_run_and_dump(tmp_path):
+    """A plain `bench.py` run (no --full) times only the headline loop: the line carries the driver's keys and none of the side legs;
+    --steps sets the timed steps; --dump-outputs writes the arrays of the last timed step, the same values run after run, and the
+    spectral ones hold the benchmark harmonic after its round trips."""
+    import json
+    import sys
+    outs = []
+    for i in range(2):
+        d = tmp_path / ("dump%d" % i)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--nsmax", "159", "--nlev", "10", "--nfld", "2",
+                            "--steps", str(3 + i), "--warmup", "1", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stdout + p.stderr
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout + p.stderr
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 + i and out["unit"] == "pairs/s" and out["dtype"] == "f64" and out["higher_is_better"] is True
+        assert abs(out["ms_per_step"] * out["value"] - 1000.0) < 1e-6 * 1000 and out["spectral_norm_rel_error"] < 1e-12
+        for k in ("dense_timing", "api_level", "cpu_baseline", "cpu_baseline_blas", "dense", "fortran_device_resident"):
+            assert k not in out, k
+        outs.append({n: np.load(str(d / (n + ".npy"))) for n in ("gpuv", "gp3a", "gp2", "spvor", "spdiv", "spsc3a", "spsc2")})
+    assert sum(a.nbytes for a in outs[0].values()) <= 64e6
+    for n, a in outs[0].items():
+        b = outs[1][n]
+        assert a.dtype == np.float64 and a.shape == b.shape and np.isfinite(a).all(), n
+        assert np.abs(a - b).max() <= 1e-10 * np.abs(a).max(), n
+    assert outs[0]["spsc2"].shape == (160 * 161, 1) and abs(outs[0]["spsc2"].max() - 1.0) < 1e-10
+    assert outs[0]["gp3a"].shape[:3] == (1, 2, 10) and np.abs(outs[0]["gp3a"]).max() > 0.1
+
+
 def test_native_rccl_transport():
     """ectrans_amd/rccl/emi_rccl_hook.c: the all-to-all-v as grouped ncclSend / ncclRecv on the library's stream, for hosts
     without Python (tests/rccl/test_rccl_hook.c, the RCCL twin of the MPI host).  One task here exercises
@@ -371,13 +400,13 @@ def test_fortran_shim_with_two_vsets(ntasks):
 
 
 def test_bench_line_contract():
-    """`bench.py` on one GPU at a small size with every leg on (oracle port, library BLAS + FFT, dense parity, host-array rate): ONE JSON line
+    """`bench.py --full` on one GPU at a small size with every leg on (oracle port, library BLAS + FFT, dense parity, host-array rate): ONE JSON line
     with the driver's keys and the two blocks this tier adds -- `roofline` (bound, achieved, peak, unit, frac, traffic) and
     `cpu_baseline` (value, unit, cores, kind, sample) -- plus `cpu_baseline_blas`, `fft_bound`, `dense`."""
     import json
     import sys
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nsmax", "159", "--nlev", "10", "--nfld", "2", "--steps", "2", "--warmup", "1"],
-                       capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nsmax", "159", "--nlev", "10", "--nfld", "2", "--steps", "2", "--warmup", "1",
+                        "--full"], capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout + p.stderr
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout + p.stderr

@@ -22,7 +22,7 @@ rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_L
 # 3b. L2 hit rate per kernel: TCC_HIT_sum / (TCC_HIT_sum + TCC_MISS_sum)
 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $O/${TAG}_pmc_l2 -- python3 bench.py --precision $PREC --steps 1 --warmup 0 --no-cpu-baseline --no-api-level --no-dense-timing --no-fortran > $O/${TAG}_pmc_l2.log 2>&1
 # 4. the bench line itself, with the CPU baseline, outside any profiler
-python3 bench.py --precision $PREC $( [ "$PREC" = 4 ] && echo --no-cpu-baseline --no-api-level ) > $O/${TAG}_bench.json 2> $O/${TAG}_bench_err.log
+python3 bench.py --full --precision $PREC $( [ "$PREC" = 4 ] && echo --no-cpu-baseline --no-api-level ) > $O/${TAG}_bench.json 2> $O/${TAG}_bench_err.log
 tail -c 3000 $O/${TAG}_bench.json
 cat $O/${TAG}_pmc_traffic.txt
 find $O/${TAG}_stats -name "*kernel_stats.csv" | head -1 | xargs head -12

@@ -19,10 +19,10 @@ python3 tools/pmc_traffic.py $O/${TAG}_fp32_pmc_fetch $O/${TAG}_fp32_pmc_write $
 bash tools/pmc_fft.sh $TAG 4 > $O/${TAG}_pmc_fft_fp32_stdout.txt 2>&1
 # the bench line quotes the counter files of ITS build (source hash): put the ones just collected where bench.py looks (the box's copy of the repo)
 cp $O/${TAG}_pmc_traffic.json $O/${TAG}_pmc_fft.json $O/${TAG}_pmc_traffic_fp32.json $O/${TAG}_pmc_fft_fp32.json profiles/ 2>/dev/null
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench_tco1279_driver_cmd.json 2> $O/${TAG}_bench_driver_err.log
-python3 bench.py --nsmax 399 --nfld 4 --steps 20 --warmup 5 --no-fortran > $O/${TAG}_bench_tco399.json 2>> $O/${TAG}_bench_driver_err.log
-python3 bench.py --precision 4 --no-cpu-baseline --no-api-level > $O/${TAG}_bench_tco1279_fp32.json 2>> $O/${TAG}_bench_driver_err.log
-python3 bench.py --nsmax 2559 --precision 4 --steps 3 --warmup 1 --no-cpu-baseline --no-api-level > $O/${TAG}_bench_tco2559_fp32.json 2>> $O/${TAG}_bench_driver_err.log
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench_tco1279_driver_cmd.json 2> $O/${TAG}_bench_driver_err.log
+python3 bench.py --full --nsmax 399 --nfld 4 --steps 20 --warmup 5 --no-fortran > $O/${TAG}_bench_tco399.json 2>> $O/${TAG}_bench_driver_err.log
+python3 bench.py --full --precision 4 --no-cpu-baseline --no-api-level > $O/${TAG}_bench_tco1279_fp32.json 2>> $O/${TAG}_bench_driver_err.log
+python3 bench.py --full --nsmax 2559 --precision 4 --steps 3 --warmup 1 --no-cpu-baseline --no-api-level > $O/${TAG}_bench_tco2559_fp32.json 2>> $O/${TAG}_bench_driver_err.log
 for f in tco1279_driver_cmd tco399 tco1279_fp32 tco2559_fp32; do python3 - <<PY
 import json
 try:
