@@ -2359,181 +2359,184 @@ static int check_extents(const char *who, const ARGS &a, int nspec2, int nproma,
   return 0;
 }
 
-// INV_TRANS, and DIR_TRANSAD when adj: the adjoint of DIR_TRANS (for the inner products of the
-// reference's adjoint tests: plain sum over grid points, SPECNORM weights in spectral space) is the same
-// spectral -> grid pipeline with the Gaussian weight and 1/NLOEN applied per latitude (ledirad_mod.F90:151,183,
-// ftdirad_mod.F90:84-89) and the adjoint of UVTVD in place of VDTUV.
-static int inv_trans_impl(int kresol, const emi_invtrans_t *ap, bool adj) {
-  Plan *Pp = get_plan(kresol);
-  if (!Pp) EMI_FAIL(EMI_ERR_STATE, "INV_TRANS: unknown resolution %d", kresol);
-  if (!ap) EMI_FAIL(EMI_ERR_ARG, "INV_TRANS: null argument block");
-  Plan &P = *Pp;
-  const emi_invtrans_t &a = *ap;
-  emi_stream_t st = (emi_stream_t)a.stream;
-  const bool host = a.mem_space == EMI_MEM_HOST;
-  // ---- field accounting (inv_trans.F90:230-387)
-  const int nuv = (a.spvor || a.spdiv) ? a.nf_uv : 0;
-  if (nuv > 0 && !a.spvor) EMI_FAIL(EMI_ERR_ARG, "INV_TRANS : IF_UV > 0 BUT PSPVOR MISSING");
-  if (nuv > 0 && !a.spdiv) EMI_FAIL(EMI_ERR_ARG, "INV_TRANS : IF_UV > 0 BUT PSPDIV MISSING");
-  std::vector<ScalarRef> sc;
-  if (enumerate_scalars(a, "INV_TRANS", sc)) return EMI_ERR_ARG;
-  const int nsc = (int)sc.size();
-  bool lscders = a.ldscders && nsc > 0, lvorgp = a.ldvorgp != 0, ldivgp = a.lddivgp != 0, luvder = a.lduvder && nuv > 0;
-  if (lvorgp) ldivgp = true;  // inv_trans.F90:350
-  const int nproma = a.kproma > 0 ? a.kproma : P.ngptot;
-  const int ngpblks = (P.ngptot - 1) / nproma + 1;
-  int if_gp = 2 * nuv + nsc + (lscders ? 2 * nsc : 0) + ((nuv && lvorgp) ? nuv : 0) + ((nuv && ldivgp) ? nuv : 0) + (luvder ? 2 * nuv : 0);
-  if (a.gp) {
-    if (a.gpuv || a.gp3a || a.gp3b || a.gp2) EMI_FAIL(EMI_ERR_ARG, "INV_TRANS:PGP AND PGPUV/PGP3A/PGP3B/PGP2 CAN NOT BOTH BE PRESENT");
-    if (a.gp_nfld < if_gp) EMI_FAIL(EMI_ERR_ARG, "INV_TRANS:SECOND DIMENSION OF PGP TOO SMALL (%d < %d)", a.gp_nfld, if_gp);
+// One transform call, whichever public block it came in: emi_invtrans_t (INV_TRANS, INV_TRANSAD) or emi_dirtrans_t (DIR_TRANS,
+// DIR_TRANSAD).  The pipeline that runs it decides which side is read: the spectral arrays (inverse) or the grid arrays (direct).
+struct Call {
+  int mem_space;
+  emi_stream_t stream;
+  const emi_extents_t *ext;
+  const emi_vsets_t *vsets;
+  int kproma;
+  void *spvor, *spdiv, *spscalar, *spsc3a, *spsc3b, *spsc2;
+  int nf_uv, nf_scalar, sc3a_nlev, sc3a_nvar, sc3b_nlev, sc3b_nvar, nf_sc2;
+  void *gp, *gpuv, *gp3a, *gp3b, *gp2;
+  int gp_nfld;
+  int ldscders, ldvorgp, lddivgp, lduvder;  // LDSCDERS, LDVORGP, LDDIVGP, LDUVDER: 0 from an emi_dirtrans_t
+};
+template <class A>
+static Call to_call(const A &a) {
+  Call c{a.mem_space, (emi_stream_t)a.stream, a.ext, a.vsets, a.kproma,
+         (void *)a.spvor, (void *)a.spdiv, (void *)a.spscalar, (void *)a.spsc3a, (void *)a.spsc3b, (void *)a.spsc2,
+         a.nf_uv, a.nf_scalar, a.sc3a_nlev, a.sc3a_nvar, a.sc3b_nlev, a.sc3b_nvar, a.nf_sc2,
+         (void *)a.gp, (void *)a.gpuv, (void *)a.gp3a, (void *)a.gp3b, (void *)a.gp2, a.gp_nfld, 0, 0, 0, 0};
+  if constexpr (std::is_same<A, emi_invtrans_t>::value) c.ldscders = a.ldscders, c.ldvorgp = a.ldvorgp, c.lddivgp = a.lddivgp, c.lduvder = a.lduvder;
+  return c;
+}
+
+struct VGroups {  // the global fields of a call with V-sets (v_groups)
+  int nuv_g = 0;
+  std::vector<int> ouv;            // owner V-set (0-based) of every global u/v field
+  std::vector<ScalarRef> sc_g;     // global scalars in the reference's order
+  std::vector<int> osc;            // their owners
+  int nsc_g[4] = {0, 0, 0, 0};     // global counts: PSPSCALAR fields, PSPSC2 fields, PSPSC3A levels, PSPSC3B levels
+  int nvar3a = 0, nvar3b = 0;      // variables of PSPSC3A / PSPSC3B = IF_SC3A_G3 / IF_SC3B_G3 (inv_trans.F90:277, 310): the same on every task
+};
+
+// Field accounting of a call (inv_trans.F90:230-387, dir_trans.F90:290-303) over the call's own arrays (vg == nullptr) or over the
+// global fields of all V-sets (vg), and the reference's checks that the grid arrays these fields need are present.
+struct Fields {
+  int nuv = 0;                // u/v fields (IF_UV)
+  std::vector<ScalarRef> sc;  // scalar fields in the reference's order
+  int nf2 = 0, nlev3a = 0, nvar3a = 0, nlev3b = 0, nvar3b = 0;  // the layout of PGP2 / PGP3A / PGP3B (before the factor dmul)
+  bool scders = false, vorgp = false, divgp = false, uvder = false;  // the options in effect
+  // IF_UV_PAR; 3 with LDSCDERS (IF_SC2_G, IF_SC3A_G3 and IF_SC3B_G3 are tripled, inv_trans.F90:371-376); IF_GP
+  int nvar_uv = 2, dmul = 1, if_gp = 0;
+};
+static int account(const Call &c, const char *who, bool inverse, const VGroups *vg, Fields &f) {
+  int need[4];  // fields of PSPSCALAR, PSPSC2, PSPSC3A, PSPSC3B that need a grid array
+  if (vg) {
+    f.nuv = vg->nuv_g, f.sc = vg->sc_g;
+    f.nf2 = vg->nsc_g[1], f.nlev3a = vg->nsc_g[2], f.nvar3a = vg->nvar3a, f.nlev3b = vg->nsc_g[3], f.nvar3b = vg->nvar3b;
+    need[0] = vg->nsc_g[0], need[1] = f.nf2, need[2] = f.nlev3a * f.nvar3a, need[3] = f.nlev3b * f.nvar3b;
   } else {
-    if (nuv > 0 && !a.gpuv) EMI_FAIL(EMI_ERR_ARG, "INV_TRANS:PGPUV MISSING");
-    if (a.spscalar && nsc > 0) EMI_FAIL(EMI_ERR_ARG, "INV_TRANS:PGP MISSING (PSPSCALAR needs PGP)");
-    if (a.spsc2 && a.nf_sc2 > 0 && !a.gp2) EMI_FAIL(EMI_ERR_ARG, "INV_TRANS:PGP2 MISSING");
-    if (a.spsc3a && a.sc3a_nlev * a.sc3a_nvar > 0 && !a.gp3a) EMI_FAIL(EMI_ERR_ARG, "INV_TRANS:PGP3A MISSING");
-    if (a.spsc3b && a.sc3b_nlev * a.sc3b_nvar > 0 && !a.gp3b) EMI_FAIL(EMI_ERR_ARG, "INV_TRANS:PGP3B MISSING");
+    f.nuv = (c.spvor || c.spdiv) ? c.nf_uv : 0;
+    if (inverse && f.nuv > 0 && !c.spvor) EMI_FAIL(EMI_ERR_ARG, "%s : IF_UV > 0 BUT PSPVOR MISSING", who);
+    if (inverse && f.nuv > 0 && !c.spdiv) EMI_FAIL(EMI_ERR_ARG, "%s : IF_UV > 0 BUT PSPDIV MISSING", who);
+    if (!inverse && f.nuv > 0 && (!c.spvor || !c.spdiv)) EMI_FAIL(EMI_ERR_ARG, "%s : IF_UV > 0 BUT PSPVOR OR PSPDIV MISSING", who);
+    if (enumerate_scalars(c, who, f.sc)) return EMI_ERR_ARG;
+    f.nf2 = c.nf_sc2, f.nlev3a = c.sc3a_nlev, f.nvar3a = c.sc3a_nvar, f.nlev3b = c.sc3b_nlev, f.nvar3b = c.sc3b_nvar;
+    need[0] = c.spscalar ? (int)f.sc.size() : 0, need[1] = c.spsc2 ? f.nf2 : 0;
+    need[2] = c.spsc3a ? f.nlev3a * f.nvar3a : 0, need[3] = c.spsc3b ? f.nlev3b * f.nvar3b : 0;
   }
-  if (if_gp == 0) return EMI_SUCCESS;
-  const int nvar_uv = ((nuv && lvorgp) ? 1 : 0) + ((nuv && ldivgp) ? 1 : 0) + 2 + (luvder ? 2 : 0);  // IF_UV_PAR
-  const int dmul = lscders ? 3 : 1;
-  int uv_dim3 = nvar_uv;
-  if (check_extents(adj ? "DIR_TRANSAD" : "INV_TRANS", a, P.nspec2, nproma, ngpblks, nuv, nvar_uv, dmul, &uv_dim3)) return EMI_ERR_ARG;
-  if (set_lds_attrs()) return EMI_ERR_RUNTIME;
-  if (plan_begin(P, st)) return EMI_ERR_RUNTIME;
+  const int nuv = f.nuv, nsc = (int)f.sc.size();
+  f.scders = c.ldscders && nsc > 0;
+  f.vorgp = c.ldvorgp && nuv > 0;
+  f.divgp = (c.lddivgp || c.ldvorgp) && nuv > 0;  // inv_trans.F90:350
+  f.uvder = c.lduvder && nuv > 0;
+  f.nvar_uv = 2 + (f.vorgp ? 1 : 0) + (f.divgp ? 1 : 0) + (f.uvder ? 2 : 0);
+  f.dmul = f.scders ? 3 : 1;
+  f.if_gp = nuv * f.nvar_uv + nsc * f.dmul;
+  if (vg && f.if_gp == 0) return 0;  // V-sets: no fields on any task, no array to check
+  if (c.gp) {
+    if (c.gpuv || c.gp3a || c.gp3b || c.gp2) EMI_FAIL(EMI_ERR_ARG, "%s:PGP AND PGPUV/PGP3A/PGP3B/PGP2 CAN NOT BOTH BE PRESENT", who);
+    if (c.gp_nfld < f.if_gp) EMI_FAIL(EMI_ERR_ARG, "%s:SECOND DIMENSION OF PGP TOO SMALL (%d < %d)", who, c.gp_nfld, f.if_gp);
+  } else {
+    if (nuv > 0 && !c.gpuv) EMI_FAIL(EMI_ERR_ARG, "%s:PGPUV MISSING", who);
+    if (need[0] > 0) EMI_FAIL(EMI_ERR_ARG, "%s:PGP MISSING (PSPSCALAR needs PGP)", who);
+    if (need[1] > 0 && !c.gp2) EMI_FAIL(EMI_ERR_ARG, "%s:PGP2 MISSING", who);
+    if (need[2] > 0 && !c.gp3a) EMI_FAIL(EMI_ERR_ARG, "%s:PGP3A MISSING", who);
+    if (need[3] > 0 && !c.gp3b) EMI_FAIL(EMI_ERR_ARG, "%s:PGP3B MISSING", who);
+  }
+  return 0;
+}
 
-  // ---- stage host arrays
-  HostStage hs(P.esz);
-  const size_t ns2 = P.nspec2;
-  const void *d_vor = hs.in(a.spvor, ns2 * a.nf_uv, host && nuv, st), *d_div = hs.in(a.spdiv, ns2 * a.nf_uv, host && nuv, st);
-  const void *d_sc[4] = {hs.in(a.spscalar, ns2 * a.nf_scalar, host, st), hs.in(a.spsc2, ns2 * a.nf_sc2, host, st),
-                           hs.in(a.spsc3a, ns2 * a.sc3a_nlev * a.sc3a_nvar, host, st),
-                           hs.in(a.spsc3b, ns2 * a.sc3b_nlev * a.sc3b_nvar, host, st)};
-  const size_t gsz = (size_t)nproma * ngpblks;
-  const bool gpad = gsz != (size_t)P.ngptot;  // last NPROMA block padded: those elements are not written
-  void *d_gp = hs.out(a.gp, gsz * a.gp_nfld, host, gpad || a.gp_nfld > if_gp, st);
-  void *d_gpuv = hs.out(a.gpuv, gsz * nuv * uv_dim3, host && nuv, gpad || uv_dim3 > nvar_uv, st);
-  void *d_gp2 = hs.out(a.gp2, gsz * a.nf_sc2 * dmul, host, gpad, st);
-  void *d_gp3a = hs.out(a.gp3a, gsz * a.sc3a_nlev * a.sc3a_nvar * dmul, host, gpad, st);
-  void *d_gp3b = hs.out(a.gp3b, gsz * a.sc3b_nlev * a.sc3b_nvar * dmul, host, gpad, st);
-  if (hs.failed) EMI_FAIL(EMI_ERR_RUNTIME, "INV_TRANS: cannot stage the host arrays through device memory (%s)", emi_last_error());
-
-  // ---- Legendre-space fields (ltinv_mod.F90:166-262): [vor][div] u v scalars [nsders]
-  std::vector<SpecSrc> lt;
-  auto sc_src = [&](const ScalarRef &r, int kind) {
-    SpecSrc s{};
-    s.kind = kind;
-    switch (r.arr) {
-      case 0: s.a = d_sc[0]; s.sa = a.nf_scalar; s.ia = r.lev; break;
-      case 1: s.a = d_sc[1]; s.sa = a.nf_sc2; s.ia = r.lev; break;
-      case 2: s.a = (const char *)d_sc[2] + (size_t)r.var * ns2 * a.sc3a_nlev * P.esz; s.sa = a.sc3a_nlev; s.ia = r.lev; break;
-      default: s.a = (const char *)d_sc[3] + (size_t)r.var * ns2 * a.sc3b_nlev * P.esz; s.sa = a.sc3b_nlev; s.ia = r.lev; break;
+// The grid-point fields of a call in the reference's order (inv_trans.F90:352-387, ftinv_ctl_mod.F90:228-262, trltog_mod.F90:632-690):
+// [vor] [div] u v scalars [N-S derivatives] [u, v E-W derivatives] [scalar E-W derivatives], over PGP or over PGPUV (uv_dim3
+// variables) / PGP2 / PGP3A / PGP3B.  Every field carries its group and its index in the group (the level of a u/v group, the
+// position in Fields::sc of a scalar group).
+enum { GF_VOR, GF_DIV, GF_U, GF_V, GF_SC, GF_NSD, GF_UEW, GF_VEW, GF_SCEW, GF_N };
+static bool gf_uv(int grp) { return grp != GF_SC && grp != GF_NSD && grp != GF_SCEW; }
+struct GridRef {
+  GridFld g;
+  int grp, i;
+};
+static void grid_fields(const Fields &f, const Call &d, int uv_dim3, std::vector<GridRef> &out) {
+  out.clear();
+  const int nuv = f.nuv;
+  int uvvar = 0;  // the next variable of PGPUV
+  auto add = [&](int grp, int i, int mode, void *base, int nf_arr, int fidx) {
+    GridFld g{};
+    if (d.gp) base = d.gp, nf_arr = d.gp_nfld, fidx = (int)out.size();
+    g.base = base, g.nf_arr = nf_arr, g.fidx = fidx, g.mode = mode;
+    out.push_back({g, grp, i});
+  };
+  auto uv = [&](int grp, int mode) {
+    for (int i = 0; i < nuv; i++) add(grp, i, mode, d.gpuv, nuv * uv_dim3, uvvar * nuv + i);
+    uvvar++;
+  };
+  auto sc = [&](int grp, int kder, int mode) {  // derivative block kder of every scalar (0 value, 1 N-S, 2 E-W)
+    for (int i = 0; i < (int)f.sc.size(); i++) {
+      const ScalarRef &r = f.sc[i];
+      if (r.arr == 1) add(grp, i, mode, d.gp2, f.nf2 * f.dmul, r.lev + kder * f.nf2);
+      else if (r.arr == 2) add(grp, i, mode, d.gp3a, f.nlev3a * f.nvar3a * f.dmul, (r.var + kder * f.nvar3a) * f.nlev3a + r.lev);
+      else add(grp, i, mode, d.gp3b, f.nlev3b * f.nvar3b * f.dmul, (r.var + kder * f.nvar3b) * f.nlev3b + r.lev);
     }
-    return s;
   };
-  int i_vor = -1, i_div = -1, i_u = -1, i_v = -1, i_sc = -1, i_nsd = -1;
-  if (nuv) {
-    auto uvsrc = [&](int i, int kind) {
-      SpecSrc s{};
-      s.kind = kind;
-      s.a = d_vor; s.sa = a.nf_uv; s.ia = i;
-      s.b = d_div; s.sb = a.nf_uv; s.ib = i;
-      if (kind == SPK_COPY + 100) { s.kind = SPK_COPY; s.a = d_div; }
-      return s;
-    };
-    if (lvorgp) { i_vor = (int)lt.size(); for (int i = 0; i < nuv; i++) lt.push_back(uvsrc(i, SPK_COPY)); }
-    if (ldivgp) { i_div = (int)lt.size(); for (int i = 0; i < nuv; i++) lt.push_back(uvsrc(i, SPK_COPY + 100)); }
-    i_u = (int)lt.size(); for (int i = 0; i < nuv; i++) lt.push_back(uvsrc(i, adj ? SPK_U_AD : SPK_U));
-    i_v = (int)lt.size(); for (int i = 0; i < nuv; i++) lt.push_back(uvsrc(i, adj ? SPK_V_AD : SPK_V));
-  }
-  if (nsc) {
-    i_sc = (int)lt.size();
-    for (auto &r : sc) lt.push_back(sc_src(r, SPK_COPY));
-    if (lscders) { i_nsd = (int)lt.size(); for (auto &r : sc) lt.push_back(sc_src(r, SPK_NSD)); }
-  }
-  const int nlt = (int)lt.size();
-  // ---- grid fields (ftinv_ctl_mod.F90:228-262 order) with their destination arrays
-  struct GOut { GridFld g; int lt; };
-  std::vector<GOut> gout;
-  int gcount = 0;
-  auto dest_uv = [&](int var, int lev) {
-    GridFld g{};
-    if (d_gp) { g.base = d_gp; g.nf_arr = a.gp_nfld; g.fidx = gcount; }
-    else { g.base = d_gpuv; g.nf_arr = nuv * uv_dim3; g.fidx = var * nuv + lev; }
-    return g;
-  };
-  auto dest_sc = [&](int isc, int kder) {
-    GridFld g{};
-    if (d_gp) { g.base = d_gp; g.nf_arr = a.gp_nfld; g.fidx = gcount; return g; }
-    const ScalarRef &r = sc[isc];
-    if (r.arr == 1) { g.base = d_gp2; g.nf_arr = a.nf_sc2 * dmul; g.fidx = r.lev + kder * a.nf_sc2; }
-    else if (r.arr == 2) { g.base = d_gp3a; g.nf_arr = a.sc3a_nlev * a.sc3a_nvar * dmul; g.fidx = (r.var + kder * a.sc3a_nvar) * a.sc3a_nlev + r.lev; }
-    else { g.base = d_gp3b; g.nf_arr = a.sc3b_nlev * a.sc3b_nvar * dmul; g.fidx = (r.var + kder * a.sc3b_nvar) * a.sc3b_nlev + r.lev; }
-    return g;
-  };
-  int uvvar = 0;
-  auto push = [&](GridFld g, int mode, int src) { g.mode = mode; g.src = src; gout.push_back({g, src}); gcount++; };
-  if (nuv) {
-    if (lvorgp) { for (int i = 0; i < nuv; i++) push(dest_uv(uvvar, i), GM_PLAIN, i_vor + i); uvvar++; }
-    if (ldivgp) { for (int i = 0; i < nuv; i++) push(dest_uv(uvvar, i), GM_PLAIN, i_div + i); uvvar++; }
-    for (int i = 0; i < nuv; i++) push(dest_uv(uvvar, i), GM_ACOS, i_u + i);
-    uvvar++;
-    for (int i = 0; i < nuv; i++) push(dest_uv(uvvar, i), GM_ACOS, i_v + i);
-    uvvar++;
-  }
-  for (int i = 0; i < nsc; i++) push(dest_sc(i, 0), GM_PLAIN, i_sc + i);
-  if (lscders) for (int i = 0; i < nsc; i++) push(dest_sc(i, 1), GM_ACOS, i_nsd + i);
-  if (luvder) {
-    for (int i = 0; i < nuv; i++) push(dest_uv(uvvar, i), GM_EWDER_UV, i_u + i);
-    uvvar++;
-    for (int i = 0; i < nuv; i++) push(dest_uv(uvvar, i), GM_EWDER_UV, i_v + i);
-    uvvar++;
-  }
-  if (lscders) for (int i = 0; i < nsc; i++) push(dest_sc(i, 2), GM_EWDER, i_sc + i);
+  if (f.vorgp) uv(GF_VOR, GM_PLAIN);
+  if (f.divgp) uv(GF_DIV, GM_PLAIN);
+  uv(GF_U, GM_ACOS);
+  uv(GF_V, GM_ACOS);
+  sc(GF_SC, 0, GM_PLAIN);
+  if (f.scders) sc(GF_NSD, 1, GM_ACOS);
+  if (f.uvder) uv(GF_UEW, GM_EWDER_UV), uv(GF_VEW, GM_EWDER_UV);
+  if (f.scders) sc(GF_SCEW, 2, GM_EWDER);
+}
 
-  // ---- batches over Legendre-space fields, software-pipelined over two streams
-  const int depth = pipeline_depth(P, nlt);
-  const int bsz = pick_batch(P, nlt, depth);
-  const int nbat = (nlt + bsz - 1) / bsz;
-  const bool piped = depth > 1 && nbat > 1;
-  // The 64-field column tiles of the call are dealt evenly to the batches and every batch has its own row width
-  // (2 x its tiles x 64 reals): no batch computes, stores or exchanges columns of another batch's width (with
-  // batches of ceil(fields / nbat) rounded up to 64 the 4 x 448 columns of a 1645-field call were 9 % padding).
-  const int tiles_total = (nlt + 63) / 64;
-  const int bfpad = 64 * ((tiles_total + nbat - 1) / nbat);  // widest batch
+// The arrays of a call on the device (d: c with device pointers).  Host arrays are staged through device memory, the input side
+// (the spectral arrays of the inverse, the grid arrays of the direct) copied in.  An output array is preloaded where the call
+// does not write all of it: the padding of the last NPROMA block (gpad), a PGP with more fields than IF_GP, a PGPUV with more
+// variables than IF_UV_PAR.  uv_sp: stage PSPVOR / PSPDIV (the W-set transform only with u/v fields, the V-set one always).
+static int stage(const Plan &P, HostStage &hs, const Call &c, const char *who, bool inverse, bool uv_sp, const Fields &f, size_t gsz, bool gpad,
+                 int uv_dim3, Call &d) {
+  const bool host = c.mem_space == EMI_MEM_HOST;
+  const emi_stream_t st = c.stream;
+  const size_t ns2 = P.nspec2;
+  auto sp = [&](void *h, size_t nf, bool on) { return inverse ? (void *)hs.in(h, ns2 * nf, on, st) : hs.out(h, ns2 * nf, on, false, st); };
+  auto gr = [&](void *h, size_t nf, bool on, bool pre) { return inverse ? hs.out(h, gsz * nf, on, pre, st) : (void *)hs.in(h, gsz * nf, on, st); };
+  d = c;
+  d.mem_space = EMI_MEM_DEVICE;
+  d.spvor = sp(c.spvor, c.nf_uv, uv_sp), d.spdiv = sp(c.spdiv, c.nf_uv, uv_sp);
+  d.spscalar = sp(c.spscalar, c.nf_scalar, host), d.spsc2 = sp(c.spsc2, c.nf_sc2, host);
+  d.spsc3a = sp(c.spsc3a, (size_t)c.sc3a_nlev * c.sc3a_nvar, host), d.spsc3b = sp(c.spsc3b, (size_t)c.sc3b_nlev * c.sc3b_nvar, host);
+  d.gp = gr(c.gp, c.gp_nfld, host, gpad || c.gp_nfld > f.if_gp);
+  d.gpuv = gr(c.gpuv, (size_t)f.nuv * uv_dim3, host && f.nuv, gpad || uv_dim3 > f.nvar_uv);
+  d.gp2 = gr(c.gp2, (size_t)f.nf2 * f.dmul, host, gpad);
+  d.gp3a = gr(c.gp3a, (size_t)f.nlev3a * f.nvar3a * f.dmul, host, gpad);
+  d.gp3b = gr(c.gp3b, (size_t)f.nlev3b * f.nvar3b * f.dmul, host, gpad);
+  if (hs.failed) EMI_FAIL(EMI_ERR_RUNTIME, "%s: cannot stage the host arrays through device memory (%s)", who, emi_last_error());
+  return 0;
+}
+
+// One field batch of a call: its row width, its field descriptors in the call's upload and its Legendre tile map.
+struct Batch {
+  int ldw = 0, ntiles = 0;                 // row width (2 x 64 x its column tiles); the column tiles that hold fields
+  size_t off_g = 0, off_s = 0, off_f = 0;  // offsets of its GridFld, of its SpecSrc (inverse) or SpecDst (direct), of its FuseDst
+  int ng = 0, ns = 0;                      // numbers of GridFld and of SpecSrc / SpecDst
+  LegMaps *maps = nullptr;
+};
+// appends n descriptors to the upload of a call, 256-byte aligned, and returns their offset
+template <class T>
+static size_t append_desc(std::vector<char> &hdesc, const T *p, size_t n) {
+  const size_t off = hdesc.size();
+  hdesc.resize(off + (n * sizeof(T) + 255) / 256 * 256);
+  if (n) memcpy(hdesc.data() + off, p, n * sizeof(T));
+  return off;
+}
+
+// Runs the batches of a call: first(batch, stream, FBl, FBf), the exchange between the Fourier buffers (several tasks), then
+// last(batch, stream, FBl, FBf, done).  The inverse runs Legendre (stream A), TRMTOL, FFT (stream B); the direct FFT (B), TRLTOM,
+// Legendre (A).  Several batches are software-pipelined over the three library streams (A, B, X for the exchange), forked from
+// and joined to the caller's stream.  Events of batch ib: 3 ib = first stage done, 3 ib + 1 = last stage done (recorded where the
+// last stage calls done()), 3 ib + 2 = exchange done.  Both Fourier buffers are double buffered ([ib & 1]); one task: FBf == FBl
+// and there is no exchange.
+template <class First, class Last>
+static int run_batches(Plan &P, emi_stream_t st, bool inverse, bool piped, int bfpad, std::vector<Batch> &bats, const std::vector<char> &hdesc,
+                       First first, Last last) {
   if (ensure_work(P, bfpad, piped ? 2 : 1, st)) return EMI_ERR_RUNTIME;
-  const int ldw_max = 2 * bfpad;
-  // all descriptors of the call in one upload
-  struct Bat { size_t off_l, off_g; int nl, ng, ldw; };
-  std::vector<Bat> bats;
-  std::vector<char> hdesc;
-  for (int ibat = 0, b0 = 0; ibat < nbat; ibat++) {
-    const int tiles_b = tiles_total / nbat + (ibat < tiles_total % nbat ? 1 : 0);
-    const int nb = std::min(64 * tiles_b, nlt - b0);
-    std::vector<GridFld> bg;
-    for (auto &go : gout)
-      if (go.lt >= b0 && go.lt < b0 + nb) {
-        GridFld g = go.g;
-        g.src = go.lt - b0;
-        bg.push_back(g);
-      }
-    Bat bt{};
-    bt.nl = nb;
-    bt.ldw = 2 * 64 * tiles_b;
-    bt.ng = (int)bg.size();
-    bt.off_l = hdesc.size();
-    hdesc.resize(bt.off_l + ((size_t)nb * sizeof(SpecSrc) + 255) / 256 * 256);
-    memcpy(hdesc.data() + bt.off_l, lt.data() + b0, (size_t)nb * sizeof(SpecSrc));
-    bt.off_g = hdesc.size();
-    hdesc.resize(bt.off_g + (bg.size() * sizeof(GridFld) + 255) / 256 * 256);
-    if (!bg.empty()) memcpy(hdesc.data() + bt.off_g, bg.data(), bg.size() * sizeof(GridFld));
-    bats.push_back(bt);
-    b0 += nb;
-  }
   // Legendre tile maps per batch: a batch with fewer fields than the row width (the last one of a call) only
   // gets the column tiles that hold fields (built before anything is queued or forked: a new map is a blocking upload)
-  std::vector<LegMaps *> bmaps(nbat, nullptr);
-  for (int ib = 0; ib < nbat; ib++)
-    if (leg_tilemaps(P, (bats[ib].nl + 63) / 64, &bmaps[ib])) return EMI_ERR_RUNTIME;
+  for (Batch &bt : bats)
+    if (leg_tilemaps(P, bt.ntiles, &bt.maps)) return EMI_ERR_RUNTIME;
   if (upload_desc(P, hdesc, st)) return EMI_ERR_RUNTIME;
   emi_stream_t sA = st, sB = st, sX = st;
   if (piped) {
@@ -2544,179 +2547,167 @@ static int inv_trans_impl(int kresol, const emi_invtrans_t *ap, bool adj) {
     g_pipe.begin(st);
   }
   g_pt.begin(G.profile != 0, G.profile == 2);
-  // Events of batch ib: 3 ib = Legendre done, 3 ib + 1 = FFT done, 3 ib + 2 = exchange done.  Both
-  // Fourier buffers are double buffered ([ib & 1]); one task: FBf == FBl and there is no exchange.
+  const emi_stream_t s1 = inverse ? sA : sB, s2 = inverse ? sB : sA;  // first and last stage
   const bool dist = P.nproc > 1;
   // buffer strides for the widest batch (+ the zero row DIR_TRANS keeps behind the Legendre-side rows)
+  const int ldw_max = 2 * bfpad;
   const size_t lstride = (size_t)((dist ? P.lrows : P.frows) + 1) * ldw_max * P.esz, fstride = (size_t)P.frows * ldw_max * P.esz;
-  for (int ib = 0; ib < nbat; ib++) {
-    const Bat &bt = bats[ib];
-    const int ldw = bt.ldw, bfpad_b = bt.ldw / 2;  // this batch's row width
-    const SpecSrc *d_bl = (const SpecSrc *)((char *)P.d_desc + bt.off_l);
-    const GridFld *d_bg = (const GridFld *)((char *)P.d_desc + bt.off_g);
+  int rc = EMI_SUCCESS;
+  for (int ib = 0; ib < (int)bats.size(); ib++) {
+    const Batch &bt = bats[ib];
     char *FBl = P.d_FBL + (piped ? (size_t)(ib & 1) * lstride : 0);
     char *FBf = dist ? P.d_FBF + (piped ? (size_t)(ib & 1) * fstride : 0) : FBl;
-    // stream A: spectral pack + Legendre; FBl[ib&1] was last read by the FFT (one task) or by the
-    // exchange (several tasks) of batch ib-2
-    if (piped && ib >= 2) g_pipe.wait(3 * (ib - 2) + (dist ? 2 : 1), sA);
-    int iv;
-    {
-      EmiRange rg(EMI_LBL_LTINV);  // GSTATS 102: PRFI1B / VDTUV / SPNSDE + LEINV + ASRE1B
-      iv = g_pt.start(0, sA);
-      {
-        long long nblk = (long long)P.wrows_total * ((bfpad_b + 255) / 256);
-        EMI_LAUNCH_P(P.esz, k_prepack_inv, nblk, 256, 0, sA, P.g, d_bl, bt.nl, bfpad_b, (RT *)P.d_W, ldw, (long long)P.wrows_total);
-      }
-      g_pt.stop(iv, sA);
-      iv = g_pt.start(1, sA);
-      LegMaps *lmaps = bmaps[ib];
-      // (the wide tiles first: they are the longest of the call)
-      if (lmaps->n_inv_wide > 0)
-        EMI_LAUNCH(emi_f32::k_leg_inv_wide, lmaps->n_inv_wide, LG_THREADS, LG_LDS_BYTES + 512, sA, P.g, (const int2 *)lmaps->d_inv_wide, (const float *)P.d_W, ldw, (float *)FBl, ldw);
-      if (lmaps->n_inv > 0)
-        EMI_LAUNCH_P(P.esz, k_leg_inv, lmaps->n_inv, LG_THREADS, LG_LDS_BYTES + 512, sA, P.g, (const int2 *)lmaps->d_inv, (const RT *)P.d_W, ldw, (RT *)FBl, ldw);
-      g_pt.stop(iv, sA);
+    // the buffer the first stage writes was last read by the last stage (one task) or by the exchange (several tasks) of batch ib-2
+    if (piped && ib >= 2) g_pipe.wait(3 * (ib - 2) + (dist ? 2 : 1), s1);
+    if (first(bt, s1, FBl, FBf)) {
+      rc = EMI_ERR_RUNTIME;
+      break;
     }
-    if (piped) g_pipe.signal(3 * ib, sA);
+    if (piped) g_pipe.signal(3 * ib, s1);
     if (dist) {
-      // stream X: TRMTOL; FBf[ib&1] was last read by the FFT of batch ib-2
+      // stream X: the buffer the exchange writes was last read by the last stage of batch ib-2
       if (piped) g_pipe.wait(3 * ib, sX);
       if (piped && ib >= 2) g_pipe.wait(3 * (ib - 2) + 1, sX);
-      EmiRange rg(EMI_LBL_TRMTOL);  // GSTATS 152
-      if (exchange(P, true, ldw, sX, FBl, FBf)) {
-        if (piped) g_pipe.end(st);  // the three streams were forked from the caller's: join them before giving up
-        plan_end(P, st);
-        return EMI_ERR_RUNTIME;
+      EmiRange rg(inverse ? EMI_LBL_TRMTOL : EMI_LBL_TRLTOM);  // GSTATS 152 / 153
+      if (exchange(P, inverse, bt.ldw, sX, FBl, FBf)) {
+        rc = EMI_ERR_RUNTIME;
+        break;
       }
       if (piped) g_pipe.signal(3 * ib + 2, sX);
     }
-    // stream B: FFTs
-    if (piped) g_pipe.wait(3 * ib + (dist ? 2 : 0), sB);
-    EmiRange rgf(EMI_LBL_FTINV);  // GSTATS 107: FOURIER_IN + FSC + FTINV + TRLTOG
-    iv = g_pt.start(2, sB);
-    if (launch_fft(P, true, adj, d_bg, bt.ng, FBf, ldw, nproma, sB)) {
-      if (piped) g_pipe.end(st);
-      plan_end(P, st);
-      return EMI_ERR_RUNTIME;
+    if (piped) g_pipe.wait(3 * ib + (dist ? 2 : 0), s2);
+    auto done = [&] {
+      if (piped) g_pipe.signal(3 * ib + 1, s2);
+    };
+    if (last(bt, s2, FBl, FBf, done)) {
+      rc = EMI_ERR_RUNTIME;
+      break;
     }
-    g_pt.stop(iv, sB);
-    if (piped) g_pipe.signal(3 * ib + 1, sB);
   }
-  if (piped) g_pipe.end(st);
-  if (plan_end(P, st)) return EMI_ERR_RUNTIME;
-  if (host) hs.flush(st);
-#ifndef EMI_CPU_EMU
-  EMI_CHECK(hipGetLastError());
-#endif
-  return EMI_SUCCESS;
+  if (piped) g_pipe.end(st);  // the three streams were forked from the caller's: join them, also when giving up
+  return rc;
+}
+
+// INV_TRANS, and DIR_TRANSAD when adj: the adjoint of DIR_TRANS (for the inner products of the
+// reference's adjoint tests: plain sum over grid points, SPECNORM weights in spectral space) is the same
+// spectral -> grid pipeline with the Gaussian weight and 1/NLOEN applied per latitude (ledirad_mod.F90:151,183,
+// ftdirad_mod.F90:84-89) and the adjoint of UVTVD in place of VDTUV.
+static int inv_pipeline(Plan &P, const Call &d, const Fields &f, std::vector<GridRef> &gl, int nproma, bool adj) {
+  const size_t ns2 = P.nspec2;
+  const int nuv = f.nuv;
+  // ---- Legendre-space fields (ltinv_mod.F90:166-262): [vor][div] u v scalars [nsders]
+  std::vector<SpecSrc> lt;
+  auto sc_src = [&](const ScalarRef &r, int kind) {
+    SpecSrc s{};
+    s.kind = kind;
+    switch (r.arr) {
+      case 0: s.a = d.spscalar; s.sa = d.nf_scalar; s.ia = r.lev; break;
+      case 1: s.a = d.spsc2; s.sa = d.nf_sc2; s.ia = r.lev; break;
+      case 2: s.a = (const char *)d.spsc3a + (size_t)r.var * ns2 * d.sc3a_nlev * P.esz; s.sa = d.sc3a_nlev; s.ia = r.lev; break;
+      default: s.a = (const char *)d.spsc3b + (size_t)r.var * ns2 * d.sc3b_nlev * P.esz; s.sa = d.sc3b_nlev; s.ia = r.lev; break;
+    }
+    return s;
+  };
+  auto uvsrc = [&](int i, int kind) {
+    SpecSrc s{};
+    s.kind = kind;
+    s.a = d.spvor; s.sa = d.nf_uv; s.ia = i;
+    s.b = d.spdiv; s.sb = d.nf_uv; s.ib = i;
+    if (kind == SPK_COPY + 100) { s.kind = SPK_COPY; s.a = d.spdiv; }
+    return s;
+  };
+  int l0[GF_N] = {};  // the first Legendre-space field of every group of grid fields
+  if (f.vorgp) { l0[GF_VOR] = (int)lt.size(); for (int i = 0; i < nuv; i++) lt.push_back(uvsrc(i, SPK_COPY)); }
+  if (f.divgp) { l0[GF_DIV] = (int)lt.size(); for (int i = 0; i < nuv; i++) lt.push_back(uvsrc(i, SPK_COPY + 100)); }
+  l0[GF_U] = (int)lt.size(); for (int i = 0; i < nuv; i++) lt.push_back(uvsrc(i, adj ? SPK_U_AD : SPK_U));
+  l0[GF_V] = (int)lt.size(); for (int i = 0; i < nuv; i++) lt.push_back(uvsrc(i, adj ? SPK_V_AD : SPK_V));
+  l0[GF_SC] = (int)lt.size(); for (auto &r : f.sc) lt.push_back(sc_src(r, SPK_COPY));
+  if (f.scders) { l0[GF_NSD] = (int)lt.size(); for (auto &r : f.sc) lt.push_back(sc_src(r, SPK_NSD)); }
+  l0[GF_UEW] = l0[GF_U], l0[GF_VEW] = l0[GF_V], l0[GF_SCEW] = l0[GF_SC];  // the E-W derivatives are taken in Fourier space
+  for (GridRef &r : gl) r.g.src = l0[r.grp] + r.i;
+  const int nlt = (int)lt.size();
+
+  // ---- batches over Legendre-space fields
+  const int depth = pipeline_depth(P, nlt);
+  const int bsz = pick_batch(P, nlt, depth);
+  const int nbat = (nlt + bsz - 1) / bsz;
+  // The 64-field column tiles of the call are dealt evenly to the batches and every batch has its own row width
+  // (2 x its tiles x 64 reals): no batch computes, stores or exchanges columns of another batch's width (with
+  // batches of ceil(fields / nbat) rounded up to 64 the 4 x 448 columns of a 1645-field call were 9 % padding).
+  const int tiles_total = (nlt + 63) / 64;
+  const int bfpad = 64 * ((tiles_total + nbat - 1) / nbat);  // widest batch
+  // all descriptors of the call in one upload
+  std::vector<Batch> bats;
+  std::vector<char> hdesc;
+  for (int ibat = 0, b0 = 0; ibat < nbat; ibat++) {
+    const int tiles_b = tiles_total / nbat + (ibat < tiles_total % nbat ? 1 : 0);
+    const int nb = std::min(64 * tiles_b, nlt - b0);
+    std::vector<GridFld> bg;
+    for (const GridRef &r : gl)
+      if (r.g.src >= b0 && r.g.src < b0 + nb) {
+        bg.push_back(r.g);
+        bg.back().src -= b0;
+      }
+    Batch bt{};
+    bt.ldw = 2 * 64 * tiles_b;
+    bt.ntiles = (nb + 63) / 64;
+    bt.ns = nb, bt.off_s = append_desc(hdesc, lt.data() + b0, nb);
+    bt.ng = (int)bg.size(), bt.off_g = append_desc(hdesc, bg.data(), bg.size());
+    bats.push_back(bt);
+    b0 += nb;
+  }
+  // stream A: spectral pack + Legendre
+  auto legendre = [&](const Batch &bt, emi_stream_t s, char *FBl, char *) -> int {
+    EmiRange rg(EMI_LBL_LTINV);  // GSTATS 102: PRFI1B / VDTUV / SPNSDE + LEINV + ASRE1B
+    const int ldw = bt.ldw, bfpad_b = bt.ldw / 2;  // this batch's row width
+    const SpecSrc *d_bl = (const SpecSrc *)((char *)P.d_desc + bt.off_s);
+    int iv = g_pt.start(0, s);
+    {
+      long long nblk = (long long)P.wrows_total * ((bfpad_b + 255) / 256);
+      EMI_LAUNCH_P(P.esz, k_prepack_inv, nblk, 256, 0, s, P.g, d_bl, bt.ns, bfpad_b, (RT *)P.d_W, ldw, (long long)P.wrows_total);
+    }
+    g_pt.stop(iv, s);
+    iv = g_pt.start(1, s);
+    LegMaps *lmaps = bt.maps;
+    // (the wide tiles first: they are the longest of the call)
+    if (lmaps->n_inv_wide > 0)
+      EMI_LAUNCH(emi_f32::k_leg_inv_wide, lmaps->n_inv_wide, LG_THREADS, LG_LDS_BYTES + 512, s, P.g, (const int2 *)lmaps->d_inv_wide, (const float *)P.d_W, ldw, (float *)FBl, ldw);
+    if (lmaps->n_inv > 0)
+      EMI_LAUNCH_P(P.esz, k_leg_inv, lmaps->n_inv, LG_THREADS, LG_LDS_BYTES + 512, s, P.g, (const int2 *)lmaps->d_inv, (const RT *)P.d_W, ldw, (RT *)FBl, ldw);
+    g_pt.stop(iv, s);
+    return 0;
+  };
+  // stream B: FFTs
+  auto fft = [&](const Batch &bt, emi_stream_t s, char *, char *FBf, auto &&done) -> int {
+    EmiRange rgf(EMI_LBL_FTINV);  // GSTATS 107: FOURIER_IN + FSC + FTINV + TRLTOG
+    const int iv = g_pt.start(2, s);
+    if (launch_fft(P, true, adj, (const GridFld *)((char *)P.d_desc + bt.off_g), bt.ng, FBf, bt.ldw, nproma, s)) return EMI_ERR_RUNTIME;
+    g_pt.stop(iv, s);
+    done();
+    return 0;
+  };
+  return run_batches(P, d.stream, true, depth > 1 && nbat > 1, bfpad, bats, hdesc, legendre, fft);
 }
 
 // DIR_TRANS, and INV_TRANSAD when adj: the adjoint of INV_TRANS is the same grid -> spectral pipeline
 // without the Gaussian weight and the 1/NLOEN (ftinvad_mod.F90:77-83: "change of metric") and with the
-// adjoint of VDTUV (= -RLAPIN x UVTVD) in place of UVTVD.
-struct AdjOpts {  // INV_TRANSAD: the options of the INV_TRANS it is the adjoint of
-  bool scders = false, vorgp = false, divgp = false, uvder = false;
-};
-static int dir_trans_impl(int kresol, const emi_dirtrans_t *ap, bool adj, const AdjOpts *ao = nullptr) {
-  Plan *Pp = get_plan(kresol);
-  if (!Pp) EMI_FAIL(EMI_ERR_STATE, "DIR_TRANS: unknown resolution %d", kresol);
-  if (!ap) EMI_FAIL(EMI_ERR_ARG, "DIR_TRANS: null argument block");
-  Plan &P = *Pp;
-  const emi_dirtrans_t &a = *ap;
-  emi_stream_t st = (emi_stream_t)a.stream;
-  const bool host = a.mem_space == EMI_MEM_HOST;
-  const int nuv = (a.spvor || a.spdiv) ? a.nf_uv : 0;
-  if (nuv > 0 && (!a.spvor || !a.spdiv)) EMI_FAIL(EMI_ERR_ARG, "DIR_TRANS : IF_UV > 0 BUT PSPVOR OR PSPDIV MISSING");
-  std::vector<ScalarRef> sc;
-  if (enumerate_scalars(a, "DIR_TRANS", sc)) return EMI_ERR_ARG;
-  const int nsc = (int)sc.size();
-  const int nproma = a.kproma > 0 ? a.kproma : P.ngptot;
-  const int ngpblks = (P.ngptot - 1) / nproma + 1;
-  // INV_TRANSAD with derivative / vorticity / divergence inputs: the grid arrays have INV_TRANS's layout
-  // (inv_trans.F90:352-387: [vor][div] u v scalars [N-S derivatives] [u, v E-W derivatives] [scalar E-W derivatives])
-  const bool a_scd = ao && ao->scders && nsc > 0, a_uvd = ao && ao->uvder && nuv > 0;
-  const bool a_div = ao && (ao->divgp || ao->vorgp) && nuv > 0, a_vor = ao && ao->vorgp && nuv > 0;
-  const int nvar_uv = 2 + (a_vor ? 1 : 0) + (a_div ? 1 : 0) + (a_uvd ? 2 : 0), dmul = a_scd ? 3 : 1;
-  const int if_gp = 2 * nuv + nsc + (a_scd ? 2 * nsc : 0) + (a_vor ? nuv : 0) + (a_div ? nuv : 0) + (a_uvd ? 2 * nuv : 0);  // dir_trans.F90:303
-  if (a.gp) {
-    if (a.gpuv || a.gp3a || a.gp3b || a.gp2) EMI_FAIL(EMI_ERR_ARG, "DIR_TRANS:PGP AND PGPUV/PGP3A/PGP3B/PGP2 CAN NOT BOTH BE PRESENT");
-    if (a.gp_nfld < if_gp) EMI_FAIL(EMI_ERR_ARG, "DIR_TRANS:SECOND DIMENSION OF PGP TOO SMALL (%d < %d)", a.gp_nfld, if_gp);
-  } else {
-    if (nuv > 0 && !a.gpuv) EMI_FAIL(EMI_ERR_ARG, "DIR_TRANS:PGPUV MISSING");
-    if (a.spscalar && nsc > 0) EMI_FAIL(EMI_ERR_ARG, "DIR_TRANS:PGP MISSING (PSPSCALAR needs PGP)");
-    if (a.spsc2 && a.nf_sc2 > 0 && !a.gp2) EMI_FAIL(EMI_ERR_ARG, "DIR_TRANS:PGP2 MISSING");
-    if (a.spsc3a && a.sc3a_nlev * a.sc3a_nvar > 0 && !a.gp3a) EMI_FAIL(EMI_ERR_ARG, "DIR_TRANS:PGP3A MISSING");
-    if (a.spsc3b && a.sc3b_nlev * a.sc3b_nvar > 0 && !a.gp3b) EMI_FAIL(EMI_ERR_ARG, "DIR_TRANS:PGP3B MISSING");
-  }
-  if (if_gp == 0) return EMI_SUCCESS;
-  int uv_dim3 = nvar_uv;
-  if (check_extents(adj ? "INV_TRANSAD" : "DIR_TRANS", a, P.nspec2, nproma, ngpblks, nuv, nvar_uv, dmul, &uv_dim3)) return EMI_ERR_ARG;
-  if (set_lds_attrs()) return EMI_ERR_RUNTIME;
-  if (plan_begin(P, st)) return EMI_ERR_RUNTIME;
-
-  HostStage hs(P.esz);
-  const size_t ns2 = P.nspec2, gsz = (size_t)nproma * ngpblks;
-  void *d_vor = hs.out(a.spvor, ns2 * a.nf_uv, host && nuv), *d_div = hs.out(a.spdiv, ns2 * a.nf_uv, host && nuv);
-  void *d_sc[4] = {hs.out(a.spscalar, ns2 * a.nf_scalar, host), hs.out(a.spsc2, ns2 * a.nf_sc2, host),
-                     hs.out(a.spsc3a, ns2 * a.sc3a_nlev * a.sc3a_nvar, host), hs.out(a.spsc3b, ns2 * a.sc3b_nlev * a.sc3b_nvar, host)};
-  const void *d_gp = hs.in(a.gp, gsz * a.gp_nfld, host, st);
-  const void *d_gpuv = hs.in(a.gpuv, gsz * nuv * uv_dim3, host && nuv, st);
-  const void *d_gp2 = hs.in(a.gp2, gsz * a.nf_sc2 * dmul, host, st);
-  const void *d_gp3a = hs.in(a.gp3a, gsz * a.sc3a_nlev * a.sc3a_nvar * dmul, host, st);
-  const void *d_gp3b = hs.in(a.gp3b, gsz * a.sc3b_nlev * a.sc3b_nvar * dmul, host, st);
-  if (hs.failed) EMI_FAIL(EMI_ERR_RUNTIME, "DIR_TRANS: cannot stage the host arrays through device memory (%s)", emi_last_error());
-
+// adjoint of VDTUV (= -RLAPIN x UVTVD) in place of UVTVD.  INV_TRANSAD with derivative / vorticity / divergence inputs: the grid
+// arrays have INV_TRANS's layout (inv_trans.F90:352-387).
+static int dir_pipeline(Plan &P, const Call &d, const Fields &f, const std::vector<GridRef> &gl, int nproma, bool adj) {
+  const size_t ns2 = P.nspec2;
+  const int nuv = f.nuv, nsc = (int)f.sc.size();
   // Fourier-space fields: u(nuv) v(nuv) scalars (dir_trans.F90:301, ftdir_ctl_mod.F90); INV_TRANSAD with options adds
   // the grid vorticity / divergence, the N-S derivatives of the scalars and the E-W derivatives as further fields
-  std::vector<GridFld> gin;
-  int gcount = 0, uvvar = 0;
-  auto src_uv = [&](int i, int mode) {  // next u/v-shaped variable of PGP / PGPUV
-    GridFld g{};
-    if (d_gp) { g.base = (void *)d_gp; g.nf_arr = a.gp_nfld; g.fidx = gcount; }
-    else { g.base = (void *)d_gpuv; g.nf_arr = nuv * uv_dim3; g.fidx = uvvar * nuv + i; }
-    g.mode = mode;
-    gcount++;
-    return g;
-  };
-  auto src_sc = [&](int isc, int kder, int mode) {  // scalar isc, derivative block kder (0 value, 1 N-S, 2 E-W: trltog_mod.F90:632-690)
-    GridFld g{};
-    const ScalarRef &r = sc[isc];
-    if (d_gp) { g.base = (void *)d_gp; g.nf_arr = a.gp_nfld; g.fidx = gcount; }
-    else if (r.arr == 1) { g.base = (void *)d_gp2; g.nf_arr = a.nf_sc2 * dmul; g.fidx = r.lev + kder * a.nf_sc2; }
-    else if (r.arr == 2) { g.base = (void *)d_gp3a; g.nf_arr = a.sc3a_nlev * a.sc3a_nvar * dmul; g.fidx = (r.var + kder * a.sc3a_nvar) * a.sc3a_nlev + r.lev; }
-    else { g.base = (void *)d_gp3b; g.nf_arr = a.sc3b_nlev * a.sc3b_nvar * dmul; g.fidx = (r.var + kder * a.sc3b_nvar) * a.sc3b_nlev + r.lev; }
-    g.mode = mode;
-    gcount++;
-    return g;
-  };
   // field numbers: u_i = i, v_i = nuv + i, scalar_j = 2 nuv + j (as DIR_TRANS), then the adjoint-only inputs
-  std::vector<GridFld> g_vor, g_div, g_u, g_v, g_sc, g_ns, g_uew, g_vew, g_scew;
-  if (nuv) {
-    if (a_vor) { for (int i = 0; i < nuv; i++) g_vor.push_back(src_uv(i, GM_PLAIN)); uvvar++; }
-    if (a_div) { for (int i = 0; i < nuv; i++) g_div.push_back(src_uv(i, GM_PLAIN)); uvvar++; }
-    for (int i = 0; i < nuv; i++) g_u.push_back(src_uv(i, GM_ACOS));
-    uvvar++;
-    for (int i = 0; i < nuv; i++) g_v.push_back(src_uv(i, GM_ACOS));
-    uvvar++;
-  }
-  for (int i = 0; i < nsc; i++) g_sc.push_back(src_sc(i, 0, GM_PLAIN));
-  if (a_scd) for (int i = 0; i < nsc; i++) g_ns.push_back(src_sc(i, 1, GM_ACOS));
-  if (a_uvd) {
-    for (int i = 0; i < nuv; i++) g_uew.push_back(src_uv(i, GM_EWDER_UV));
-    uvvar++;
-    for (int i = 0; i < nuv; i++) g_vew.push_back(src_uv(i, GM_EWDER_UV));
-    uvvar++;
-  }
-  if (a_scd) for (int i = 0; i < nsc; i++) g_scew.push_back(src_sc(i, 2, GM_EWDER));
-  std::vector<int> i_vor(nuv, -1), i_div(nuv, -1), i_uew(nuv, -1), i_vew(nuv, -1), i_ns(nsc, -1), i_scew(nsc, -1);
-  for (auto *v : {&g_u, &g_v, &g_sc}) gin.insert(gin.end(), v->begin(), v->end());
-  auto add = [&](const std::vector<GridFld> &v, std::vector<int> &idx) {
-    for (size_t i = 0; i < v.size(); i++) {
-      idx[i] = (int)gin.size();
-      gin.push_back(v[i]);
-    }
-  };
-  add(g_vor, i_vor), add(g_div, i_div), add(g_uew, i_uew), add(g_vew, i_vew), add(g_ns, i_ns), add(g_scew, i_scew);
+  std::vector<GridFld> gin;
+  std::vector<int> num[GF_N];  // the field number of every member of a group (-1: absent)
+  for (int grp = 0; grp < GF_N; grp++) num[grp].assign(gf_uv(grp) ? nuv : nsc, -1);
+  for (int grp : {GF_U, GF_V, GF_SC, GF_VOR, GF_DIV, GF_UEW, GF_VEW, GF_NSD, GF_SCEW})
+    for (const GridRef &r : gl)
+      if (r.grp == grp) {
+        num[grp][r.i] = (int)gin.size();
+        gin.push_back(r.g);
+      }
   const int kf_total = (int)gin.size();
   // batches of whole atoms: {u_i, v_i [, their adjoint-only companions]} and {scalar_j [, its N-S and E-W inputs]}
   const int natoms = nuv + nsc;
@@ -2729,11 +2720,11 @@ static int dir_trans_impl(int kresol, const emi_dirtrans_t *ap, bool adj, const 
       std::vector<int> fl;
       if (at < nuv) {
         fl = {at, nuv + at};
-        for (int x : {i_vor[at], i_div[at], i_uew[at], i_vew[at]})
+        for (int x : {num[GF_VOR][at], num[GF_DIV][at], num[GF_UEW][at], num[GF_VEW][at]})
           if (x >= 0) fl.push_back(x);
       } else {
         fl = {2 * nuv + (at - nuv)};
-        for (int x : {i_ns[at - nuv], i_scew[at - nuv]})
+        for (int x : {num[GF_NSD][at - nuv], num[GF_SCEW][at - nuv]})
           if (x >= 0) fl.push_back(x);
       }
       if (!cur.empty() && (int)(cur.size() + fl.size()) > cap) {
@@ -2746,14 +2737,9 @@ static int dir_trans_impl(int kresol, const emi_dirtrans_t *ap, bool adj, const 
   }
   int maxb = 0;
   for (auto &b : batches) maxb = std::max(maxb, (int)b.size());
-  const int nbat = (int)batches.size();
-  const bool piped = depth > 1 && nbat > 1;
-  const int bfpad = roundup(maxb, 64);
-  if (ensure_work(P, bfpad, piped ? 2 : 1, st)) return EMI_ERR_RUNTIME;
-  const int ldw_max = 2 * bfpad;  // row width of the widest batch; every batch has its own (2 x its fields rounded up to 64)
-  struct Bat { size_t off_g, off_o, off_f; int ng, no, ldw; };
+  const int bfpad = roundup(maxb, 64);  // every batch has its own row width (2 x its fields rounded up to 64)
   const bool fuse_dir = !(test_paths() & 4);  // plain-copy fields leave k_leg_dir's epilogue straight for the caller's arrays
-  std::vector<Bat> bats;
+  std::vector<Batch> bats;
   std::vector<char> hdesc;
   for (auto &b : batches) {
     std::vector<GridFld> bg;
@@ -2766,27 +2752,27 @@ static int dir_trans_impl(int kresol, const emi_dirtrans_t *ap, bool adj, const 
     }
     auto at_ = [&](int x) { return x >= 0 ? loc[x] : -1; };  // field number -> position in this batch's W
     for (size_t i = 0; i < b.size(); i++) {
-      int f = b[i];
-      if (f < nuv) {  // u_i -> vor_i and div_i outputs
+      int fn = b[i];
+      if (fn < nuv) {  // u_i -> vor_i and div_i outputs
         SpecDst v{};
-        v.dst = d_vor; v.stride = a.nf_uv; v.idx = f; v.kind = adj ? SPO_VOR_AD : SPO_VOR; v.src0 = loc[f]; v.src1 = loc[nuv + f];
-        v.src2 = at_(i_uew[f]); v.src3 = at_(i_vew[f]); v.src4 = at_(i_vor[f]);
+        v.dst = d.spvor; v.stride = d.nf_uv; v.idx = fn; v.kind = adj ? SPO_VOR_AD : SPO_VOR; v.src0 = loc[fn]; v.src1 = loc[nuv + fn];
+        v.src2 = at_(num[GF_UEW][fn]); v.src3 = at_(num[GF_VEW][fn]); v.src4 = at_(num[GF_VOR][fn]);
         bo.push_back(v);
-        v.dst = d_div; v.kind = adj ? SPO_DIV_AD : SPO_DIV; v.src4 = at_(i_div[f]);
+        v.dst = d.spdiv; v.kind = adj ? SPO_DIV_AD : SPO_DIV; v.src4 = at_(num[GF_DIV][fn]);
         bo.push_back(v);
-      } else if (f >= 2 * nuv && f < 2 * nuv + nsc) {
-        const int isc = f - 2 * nuv;
-        const ScalarRef &r = sc[isc];
+      } else if (fn >= 2 * nuv && fn < 2 * nuv + nsc) {
+        const int isc = fn - 2 * nuv;
+        const ScalarRef &r = f.sc[isc];
         SpecDst sd{};
         sd.kind = SPO_COPY; sd.src0 = (int)i; sd.src1 = sd.src2 = sd.src3 = sd.src4 = -1;
         switch (r.arr) {
-          case 0: sd.dst = d_sc[0]; sd.stride = a.nf_scalar; sd.idx = r.lev; break;
-          case 1: sd.dst = d_sc[1]; sd.stride = a.nf_sc2; sd.idx = r.lev; break;
-          case 2: sd.dst = (char *)d_sc[2] + (size_t)r.var * ns2 * a.sc3a_nlev * P.esz; sd.stride = a.sc3a_nlev; sd.idx = r.lev; break;
-          default: sd.dst = (char *)d_sc[3] + (size_t)r.var * ns2 * a.sc3b_nlev * P.esz; sd.stride = a.sc3b_nlev; sd.idx = r.lev; break;
+          case 0: sd.dst = d.spscalar; sd.stride = d.nf_scalar; sd.idx = r.lev; break;
+          case 1: sd.dst = d.spsc2; sd.stride = d.nf_sc2; sd.idx = r.lev; break;
+          case 2: sd.dst = (char *)d.spsc3a + (size_t)r.var * ns2 * d.sc3a_nlev * P.esz; sd.stride = d.sc3a_nlev; sd.idx = r.lev; break;
+          default: sd.dst = (char *)d.spsc3b + (size_t)r.var * ns2 * d.sc3b_nlev * P.esz; sd.stride = d.sc3b_nlev; sd.idx = r.lev; break;
         }
-        if (a_scd) {  // value + adjoint of SPNSDE on the N-S input + (-i m) x the E-W input: k_postpack_dir
-          sd.kind = SPO_SC_AD; sd.src1 = at_(i_ns[isc]); sd.src2 = at_(i_scew[isc]);
+        if (f.scders) {  // value + adjoint of SPNSDE on the N-S input + (-i m) x the E-W input: k_postpack_dir
+          sd.kind = SPO_SC_AD; sd.src1 = at_(num[GF_NSD][isc]); sd.src2 = at_(num[GF_SCEW][isc]);
           bo.push_back(sd);
         } else if (fuse_dir) {
           bf[i] = FuseDst{sd.dst, sd.stride, sd.idx};  // written by the epilogue of k_leg_dir
@@ -2795,97 +2781,76 @@ static int dir_trans_impl(int kresol, const emi_dirtrans_t *ap, bool adj, const 
         }
       }
     }
-    Bat bt{};
-    bt.ng = (int)bg.size();
+    Batch bt{};
     bt.ldw = 2 * roundup((int)b.size(), 64);
-    bt.no = (int)bo.size();
-    bt.off_g = hdesc.size();
-    hdesc.resize(bt.off_g + (bg.size() * sizeof(GridFld) + 255) / 256 * 256);
-    if (!bg.empty()) memcpy(hdesc.data() + bt.off_g, bg.data(), bg.size() * sizeof(GridFld));
-    bt.off_o = hdesc.size();
-    hdesc.resize(bt.off_o + (bo.size() * sizeof(SpecDst) + 255) / 256 * 256);
-    if (!bo.empty()) memcpy(hdesc.data() + bt.off_o, bo.data(), bo.size() * sizeof(SpecDst));
-    bt.off_f = hdesc.size();
-    hdesc.resize(bt.off_f + (bf.size() * sizeof(FuseDst) + 255) / 256 * 256);
-    if (!bf.empty()) memcpy(hdesc.data() + bt.off_f, bf.data(), bf.size() * sizeof(FuseDst));
+    bt.ntiles = ((int)b.size() + 63) / 64;  // per batch: only the column tiles that hold fields (as INV_TRANS)
+    bt.ng = (int)bg.size(), bt.off_g = append_desc(hdesc, bg.data(), bg.size());
+    bt.ns = (int)bo.size(), bt.off_s = append_desc(hdesc, bo.data(), bo.size());
+    bt.off_f = append_desc(hdesc, bf.data(), bf.size());
     bats.push_back(bt);
   }
-  std::vector<LegMaps *> bmaps(nbat, nullptr);  // per batch: only the column tiles that hold fields (as INV_TRANS)
-  for (int ib = 0; ib < nbat; ib++)
-    if (leg_tilemaps(P, (bats[ib].ng + 63) / 64, &bmaps[ib])) return EMI_ERR_RUNTIME;
-  if (upload_desc(P, hdesc, st)) return EMI_ERR_RUNTIME;
-  emi_stream_t sA = st, sB = st, sX = st;
-  if (piped) {
-    if (g_pipe.init()) return EMI_ERR_RUNTIME;
-    sA = (emi_stream_t)g_pipe.sA;
-    sB = (emi_stream_t)g_pipe.sB;
-    sX = (emi_stream_t)g_pipe.sX;
-    g_pipe.begin(st);
-  }
-  g_pt.begin(G.profile != 0, G.profile == 2);
-  // events of batch ib: 3 ib = FFT done, 3 ib + 1 = Legendre done, 3 ib + 2 = exchange done (as INV_TRANS)
-  const bool dist = P.nproc > 1;
-  // buffer strides for the widest batch, + the zero row behind the Legendre-side rows of each buffer
-  const long long lrows_call = dist ? P.lrows : P.frows;
-  const size_t lstride = (size_t)(lrows_call + 1) * ldw_max * P.esz, fstride = (size_t)P.frows * ldw_max * P.esz;
-  for (int ib = 0; ib < nbat; ib++) {
-    const Bat &bt = bats[ib];
-    const int ldw = bt.ldw;  // this batch's row width
-    const GridFld *d_bg = (const GridFld *)((char *)P.d_desc + bt.off_g);
-    const SpecDst *d_bo = (const SpecDst *)((char *)P.d_desc + bt.off_o);
-    char *FBl = P.d_FBL + (piped ? (size_t)(ib & 1) * lstride : 0);
-    char *FBf = dist ? P.d_FBF + (piped ? (size_t)(ib & 1) * fstride : 0) : FBl;
-    // stream B: FFTs; FBf[ib&1] was last read by the Legendre transform (one task) or by the exchange
-    // (several tasks) of batch ib-2
-    if (piped && ib >= 2) g_pipe.wait(3 * (ib - 2) + (dist ? 2 : 1), sB);
-    int iv;
-    {
-      EmiRange rg(EMI_LBL_FTDIR);  // GSTATS 106: TRGTOL + FTDIR + FOURIER_OUT
-      iv = g_pt.start(2, sB);
-      if (launch_fft(P, false, adj, d_bg, bt.ng, FBf, ldw, nproma, sB)) {
-        if (piped) g_pipe.end(st);
-        plan_end(P, st);
-        return EMI_ERR_RUNTIME;
-      }
-      g_pt.stop(iv, sB);
-    }
-    if (piped) g_pipe.signal(3 * ib, sB);
-    if (dist) {
-      // stream X: TRLTOM; FBl[ib&1] was last read by the Legendre transform of batch ib-2
-      if (piped) g_pipe.wait(3 * ib, sX);
-      if (piped && ib >= 2) g_pipe.wait(3 * (ib - 2) + 1, sX);
-      EmiRange rg(EMI_LBL_TRLTOM);  // GSTATS 153
-      if (exchange(P, false, ldw, sX, FBl, FBf)) {
-        if (piped) g_pipe.end(st);
-        plan_end(P, st);
-        return EMI_ERR_RUNTIME;
-      }
-      if (piped) g_pipe.signal(3 * ib + 2, sX);
-    }
-    // stream A: Legendre + spectral unpack
-    if (piped) g_pipe.wait(3 * ib + (dist ? 2 : 0), sA);
+  // stream B: FFTs
+  auto fft = [&](const Batch &bt, emi_stream_t s, char *, char *FBf) -> int {
+    EmiRange rg(EMI_LBL_FTDIR);  // GSTATS 106: TRGTOL + FTDIR + FOURIER_OUT
+    const int iv = g_pt.start(2, s);
+    if (launch_fft(P, false, adj, (const GridFld *)((char *)P.d_desc + bt.off_g), bt.ng, FBf, bt.ldw, nproma, s)) return EMI_ERR_RUNTIME;
+    g_pt.stop(iv, s);
+    return 0;
+  };
+  // stream A: Legendre + spectral unpack
+  auto legendre = [&](const Batch &bt, emi_stream_t s, char *FBl, char *, auto &&done) -> int {
     EmiRange rgl(EMI_LBL_LTDIR);  // GSTATS 103: PRFI2B + LEDIR + UVTVD + UPDSP
-    iv = g_pt.start(1, sA);
+    const int ldw = bt.ldw;  // this batch's row width
+    const long long lrows_call = P.nproc > 1 ? P.lrows : P.frows;
+    int iv = g_pt.start(1, s);
     // the zero row of this batch: row `lrows_call` in the batch's own row width (the buffer held other data before)
-    emi_dev_memset(FBl + (size_t)lrows_call * ldw * P.esz, 0, (size_t)ldw * P.esz, sA);
+    emi_dev_memset(FBl + (size_t)lrows_call * ldw * P.esz, 0, (size_t)ldw * P.esz, s);
     const FuseDst *d_bf = fuse_dir ? (const FuseDst *)((char *)P.d_desc + bt.off_f) : nullptr;
-    LegMaps *lmaps = bmaps[ib];
+    LegMaps *lmaps = bt.maps;
     if (lmaps->n_dir_wide > 0)  // (the double-precision tiles first: they are the longest of the call)
-      EMI_LAUNCH(emi_f32::k_leg_dir_wide, lmaps->n_dir_wide, LG_THREADS, leg_dir_lds_bytes(P), sA, P.g, (const int2 *)lmaps->d_dir_wide, (const float *)FBl, (int)lrows_call, ldw, (float *)P.d_W, ldw,
+      EMI_LAUNCH(emi_f32::k_leg_dir_wide, lmaps->n_dir_wide, LG_THREADS, leg_dir_lds_bytes(P), s, P.g, (const int2 *)lmaps->d_dir_wide, (const float *)FBl, (int)lrows_call, ldw, (float *)P.d_W, ldw,
                  d_bf);
     if (lmaps->n_dir > 0)
-      EMI_LAUNCH_P(P.esz, k_leg_dir, lmaps->n_dir, LG_THREADS, leg_dir_lds_bytes(P), sA, P.g, (const int2 *)lmaps->d_dir, (const RT *)FBl, (int)lrows_call, ldw, (RT *)P.d_W, ldw, d_bf);
-    g_pt.stop(iv, sA);
-    if (piped) g_pipe.signal(3 * ib + 1, sA);
-    iv = g_pt.start(0, sA);
-    if (bt.no > 0) {  // vorticity / divergence from the wind fields left in W
-      long long nblk = ((long long)P.wrows_total + 3) / 4 * ((bt.no + 63) / 64);  // block = 4 rows x 64 fields
-      EMI_LAUNCH_P(P.esz, k_postpack_dir, nblk, 256, 0, sA, P.g, d_bo, bt.no, (const RT *)P.d_W, ldw, (long long)P.wrows_total);
+      EMI_LAUNCH_P(P.esz, k_leg_dir, lmaps->n_dir, LG_THREADS, leg_dir_lds_bytes(P), s, P.g, (const int2 *)lmaps->d_dir, (const RT *)FBl, (int)lrows_call, ldw, (RT *)P.d_W, ldw, d_bf);
+    g_pt.stop(iv, s);
+    done();
+    iv = g_pt.start(0, s);
+    if (bt.ns > 0) {  // vorticity / divergence from the wind fields left in W
+      const SpecDst *d_bo = (const SpecDst *)((char *)P.d_desc + bt.off_s);
+      long long nblk = ((long long)P.wrows_total + 3) / 4 * ((bt.ns + 63) / 64);  // block = 4 rows x 64 fields
+      EMI_LAUNCH_P(P.esz, k_postpack_dir, nblk, 256, 0, s, P.g, d_bo, bt.ns, (const RT *)P.d_W, ldw, (long long)P.wrows_total);
     }
-    g_pt.stop(iv, sA);
+    g_pt.stop(iv, s);
+    return 0;
+  };
+  return run_batches(P, d.stream, false, depth > 1 && batches.size() > 1, bfpad, bats, hdesc, fft, legendre);
+}
+
+// The transform of the fields of one W-set (all fields without V-sets): checks, staging, the pipeline of the direction
+static int wset_transform(Plan &P, const Call &c, bool inverse, bool adj, const char *who) {
+  Fields f;
+  if (account(c, who, inverse, nullptr, f)) return EMI_ERR_ARG;
+  if (f.if_gp == 0) return EMI_SUCCESS;
+  const int nproma = c.kproma > 0 ? c.kproma : P.ngptot;
+  const int ngpblks = (P.ngptot - 1) / nproma + 1;
+  int uv_dim3 = f.nvar_uv;
+  if (check_extents(who, c, P.nspec2, nproma, ngpblks, f.nuv, f.nvar_uv, f.dmul, &uv_dim3)) return EMI_ERR_ARG;
+  if (set_lds_attrs()) return EMI_ERR_RUNTIME;
+  const emi_stream_t st = c.stream;
+  if (plan_begin(P, st)) return EMI_ERR_RUNTIME;
+  const bool host = c.mem_space == EMI_MEM_HOST;
+  HostStage hs(P.esz);
+  const size_t gsz = (size_t)nproma * ngpblks;
+  const bool gpad = gsz != (size_t)P.ngptot;  // last NPROMA block padded: those elements are not written
+  Call d;
+  int rc = stage(P, hs, c, who, inverse, host && f.nuv, f, gsz, gpad, uv_dim3, d);
+  if (rc == EMI_SUCCESS) {
+    std::vector<GridRef> gl;
+    grid_fields(f, d, uv_dim3, gl);
+    rc = inverse ? inv_pipeline(P, d, f, gl, nproma, adj) : dir_pipeline(P, d, f, gl, nproma, adj);
   }
-  if (piped) g_pipe.end(st);
-  if (plan_end(P, st)) return EMI_ERR_RUNTIME;
+  if (plan_end(P, st) && rc == EMI_SUCCESS) rc = EMI_ERR_RUNTIME;
+  if (rc != EMI_SUCCESS) return rc;
   if (host) hs.flush(st);
 #ifndef EMI_CPU_EMU
   EMI_CHECK(hipGetLastError());
@@ -3490,14 +3455,6 @@ struct StageBuf {  // device scratch from the staging pool
     if (p) emi_stage::release(p);
   }
 };
-struct VGroups {
-  int nuv_g = 0;
-  std::vector<int> ouv;            // owner V-set (0-based) of every global u/v field
-  std::vector<ScalarRef> sc_g;     // global scalars in the reference's order
-  std::vector<int> osc;            // their owners
-  int nsc_g[4] = {0, 0, 0, 0};     // global counts: PSPSCALAR fields, PSPSC2 fields, PSPSC3A levels, PSPSC3B levels
-  int nvar3a = 0, nvar3b = 0;      // variables of PSPSC3A / PSPSC3B = IF_SC3A_G3 / IF_SC3B_G3 (inv_trans.F90:277, 310): the same on every task
-};
 template <class ARGS>
 static int v_groups(const Plan &P, const ARGS &a, const char *who, VGroups &vg) {
   const emi_vsets_t *vs = a.vsets;
@@ -3574,51 +3531,6 @@ static int v_groups(const Plan &P, const ARGS &a, const char *who, VGroups &vg) 
   }
   return 0;
 }
-// all grid fields of the call in the reference's order, over the caller's (global-count) arrays, with their owner V-sets
-struct VGridList {
-  std::vector<GridFld> g;
-  std::vector<int> owner;
-};
-static void v_grid_fields(const VGroups &vg, bool lvorgp, bool ldivgp, bool lscders, bool luvder, void *gp, int gp_nfld, void *gpuv, int uv_dim3,
-                          void *gp2, void *gp3a, void *gp3b, VGridList &out) {
-  const int nvar3a = vg.nvar3a, nvar3b = vg.nvar3b;
-  const int nuv = vg.nuv_g, nsc = (int)vg.sc_g.size(), dmul = lscders ? 3 : 1;
-  int gcount = 0, uvvar = 0;
-  auto uvf = [&](int lev) {
-    GridFld g{};
-    if (gp) { g.base = gp; g.nf_arr = gp_nfld; g.fidx = gcount; }
-    else { g.base = gpuv; g.nf_arr = nuv * uv_dim3; g.fidx = uvvar * nuv + lev; }
-    out.g.push_back(g), out.owner.push_back(vg.ouv[lev]);
-    gcount++;
-  };
-  auto scf = [&](int isc, int kder) {
-    GridFld g{};
-    const ScalarRef &r = vg.sc_g[isc];
-    if (gp) { g.base = gp; g.nf_arr = gp_nfld; g.fidx = gcount; }
-    else if (r.arr == 1) { g.base = gp2; g.nf_arr = vg.nsc_g[1] * dmul; g.fidx = r.lev + kder * vg.nsc_g[1]; }
-    else if (r.arr == 2) { g.base = gp3a; g.nf_arr = vg.nsc_g[2] * nvar3a * dmul; g.fidx = (r.var + kder * nvar3a) * vg.nsc_g[2] + r.lev; }
-    else { g.base = gp3b; g.nf_arr = vg.nsc_g[3] * nvar3b * dmul; g.fidx = (r.var + kder * nvar3b) * vg.nsc_g[3] + r.lev; }
-    out.g.push_back(g), out.owner.push_back(vg.osc[isc]);
-    gcount++;
-  };
-  if (nuv) {
-    if (lvorgp) { for (int i = 0; i < nuv; i++) uvf(i); uvvar++; }
-    if (ldivgp) { for (int i = 0; i < nuv; i++) uvf(i); uvvar++; }
-    for (int i = 0; i < nuv; i++) uvf(i);
-    uvvar++;
-    for (int i = 0; i < nuv; i++) uvf(i);
-    uvvar++;
-  }
-  for (int i = 0; i < nsc; i++) scf(i, 0);
-  if (lscders) for (int i = 0; i < nsc; i++) scf(i, 1);
-  if (luvder && nuv) {
-    for (int i = 0; i < nuv; i++) uvf(i);
-    uvvar++;
-    for (int i = 0; i < nuv; i++) uvf(i);
-    uvvar++;
-  }
-  if (lscders) for (int i = 0; i < nsc; i++) scf(i, 2);
-}
 // pack / unpack one block of the V-exchange: nf fields x npts points between two lists of grid-field descriptors
 static int v_copy(Plan &P, const std::vector<GridFld> &src, const std::vector<GridFld> &dst, long long sp0, long long dp0, long long npts, long long snp,
                   long long dnp, std::vector<StageBuf *> &keep, emi_stream_t st) {
@@ -3642,187 +3554,81 @@ static GridFld dense_field(void *base, size_t field, long long npts, int esz) {
   return g;
 }
 
-static int inv_trans_vsets(int kresol, const emi_invtrans_t *ap, bool adj) {
-  Plan *Pp = get_plan(kresol);
-  const char *who = adj ? "DIR_TRANSAD" : "INV_TRANS";
-  if (!Pp) EMI_FAIL(EMI_ERR_STATE, "%s: unknown resolution %d", who, kresol);
-  if (!ap) EMI_FAIL(EMI_ERR_ARG, "%s: null argument block", who);
-  Plan &P = *Pp;
-  const emi_invtrans_t &a = *ap;
-  emi_stream_t st = (emi_stream_t)a.stream;
-  const bool host = a.mem_space == EMI_MEM_HOST;
+// The transform with V-sets: the W-set transform of this V-set's fields runs into (inverse) or out of (direct) a band-sized array,
+// and TRLTOG (inverse) / TRGTOL (direct) moves the fields between that array and the caller's grid arrays.
+static int vset_transform(Plan &P, const Call &c, bool inverse, bool adj, const char *who) {
+  if (!inverse && (c.ldscders || c.ldvorgp || c.lddivgp || c.lduvder))
+    EMI_FAIL(EMI_ERR_UNSUPPORTED, "INV_TRANSAD: LDSCDERS / LDVORGP / LDDIVGP / LDUVDER are not supported with NPRTRV > 1");
   VGroups vg;
-  if (v_groups(P, a, who, vg)) return EMI_ERR_ARG;
-  const int nuvg = vg.nuv_g, nscg = (int)vg.sc_g.size();
-  const bool lscders = a.ldscders && nscg > 0, lvorgp = a.ldvorgp != 0, ldivgp = a.lddivgp != 0 || lvorgp, luvder = a.lduvder && nuvg > 0;
-  const int if_gp_g = 2 * nuvg + nscg + (lscders ? 2 * nscg : 0) + ((nuvg && lvorgp) ? nuvg : 0) + ((nuvg && ldivgp) ? nuvg : 0) + (luvder ? 2 * nuvg : 0);
-  if (if_gp_g == 0) return EMI_SUCCESS;
-  const int nvar_uv = ((nuvg && lvorgp) ? 1 : 0) + ((nuvg && ldivgp) ? 1 : 0) + 2 + (luvder ? 2 : 0), dmul = lscders ? 3 : 1;
+  if (v_groups(P, c, who, vg)) return EMI_ERR_ARG;
+  Fields f;
+  if (account(c, who, inverse, &vg, f)) return EMI_ERR_ARG;
+  if (f.if_gp == 0) return EMI_SUCCESS;
   const long long myp = P.vpoints(P.me, P.mev), bandp = P.ngptot;
-  const int nproma = a.kproma > 0 ? a.kproma : (int)myp;
+  const int nproma = c.kproma > 0 ? c.kproma : (int)myp;
   const int ngpblks = (int)((myp - 1) / nproma + 1);
-  if (a.gp) {
-    if (a.gpuv || a.gp3a || a.gp3b || a.gp2) EMI_FAIL(EMI_ERR_ARG, "%s:PGP AND PGPUV/PGP3A/PGP3B/PGP2 CAN NOT BOTH BE PRESENT", who);
-    if (a.gp_nfld < if_gp_g) EMI_FAIL(EMI_ERR_ARG, "%s:SECOND DIMENSION OF PGP TOO SMALL (%d < %d)", who, a.gp_nfld, if_gp_g);
-  } else {
-    if (nuvg > 0 && !a.gpuv) EMI_FAIL(EMI_ERR_ARG, "%s:PGPUV MISSING", who);
-    if (vg.nsc_g[0] > 0) EMI_FAIL(EMI_ERR_ARG, "%s:PGP MISSING (PSPSCALAR needs PGP)", who);
-    if (vg.nsc_g[1] > 0 && !a.gp2) EMI_FAIL(EMI_ERR_ARG, "%s:PGP2 MISSING", who);
-    if (vg.nsc_g[2] * vg.nvar3a > 0 && !a.gp3a) EMI_FAIL(EMI_ERR_ARG, "%s:PGP3A MISSING", who);
-    if (vg.nsc_g[3] * vg.nvar3b > 0 && !a.gp3b) EMI_FAIL(EMI_ERR_ARG, "%s:PGP3B MISSING", who);
-  }
+  const emi_stream_t st = c.stream;
+  const bool host = c.mem_space == EMI_MEM_HOST;
   // ---- the caller's arrays on the device (spectral: local fields; grid: all fields on this task's points)
   HostStage hs(P.esz);
-  const size_t ns2 = P.nspec2, gsz = (size_t)nproma * ngpblks;
-  const bool gpad = gsz != (size_t)myp;
-  emi_invtrans_t in = a;
-  in.mem_space = EMI_MEM_DEVICE;
+  const size_t gsz = (size_t)nproma * ngpblks;
+  Call in;
+  if (stage(P, hs, c, who, inverse, host, f, gsz, gsz != (size_t)myp, f.nvar_uv, in)) return EMI_ERR_RUNTIME;
+  std::vector<GridRef> gl;
+  grid_fields(f, in, f.nvar_uv, gl);
+  std::vector<int> owner, nl(P.nprv, 0);  // the owner V-set of every grid field; the grid fields every V-set computes
+  for (const GridRef &r : gl) {
+    owner.push_back(gf_uv(r.grp) ? vg.ouv[r.i] : vg.osc[r.i]);
+    nl[owner.back()]++;
+  }
+  const int nlm = nl[P.mev];
+  // ---- the band-sized array [field][band point] of the W-set transform, and the two sides of the exchange
+  StageBuf tband((size_t)nlm * bandp * P.esz), xband((size_t)nlm * bandp * P.esz), xgrid((size_t)f.if_gp * myp * P.esz);
+  if ((nlm && (!tband.p || !xband.p)) || !xgrid.p) EMI_FAIL(EMI_ERR_RUNTIME, "%s: no device memory for the exchange between the V-sets", who);
   in.ext = nullptr;
   in.vsets = nullptr;
-  in.spvor = hs.in(a.spvor, ns2 * a.nf_uv, host, st), in.spdiv = hs.in(a.spdiv, ns2 * a.nf_uv, host, st);
-  in.spscalar = hs.in(a.spscalar, ns2 * a.nf_scalar, host, st), in.spsc2 = hs.in(a.spsc2, ns2 * a.nf_sc2, host, st);
-  in.spsc3a = hs.in(a.spsc3a, ns2 * a.sc3a_nlev * a.sc3a_nvar, host, st), in.spsc3b = hs.in(a.spsc3b, ns2 * a.sc3b_nlev * a.sc3b_nvar, host, st);
-  void *d_gp = hs.out(a.gp, gsz * a.gp_nfld, host, gpad || a.gp_nfld > if_gp_g, st);
-  void *d_gpuv = hs.out(a.gpuv, gsz * nuvg * nvar_uv, host && nuvg, gpad, st);
-  void *d_gp2 = hs.out(a.gp2, gsz * vg.nsc_g[1] * dmul, host, gpad, st);
-  void *d_gp3a = hs.out(a.gp3a, gsz * vg.nsc_g[2] * vg.nvar3a * dmul, host, gpad, st);
-  void *d_gp3b = hs.out(a.gp3b, gsz * vg.nsc_g[3] * vg.nvar3b * dmul, host, gpad, st);
-  if (hs.failed) EMI_FAIL(EMI_ERR_RUNTIME, "%s: cannot stage the host arrays through device memory (%s)", who, emi_last_error());
-  VGridList gl;
-  v_grid_fields(vg, lvorgp, ldivgp, lscders, luvder, d_gp, a.gp_nfld, d_gpuv, nvar_uv, d_gp2, d_gp3a, d_gp3b, gl);
-  std::vector<int> nl(P.nprv, 0);  // grid fields every V-set computes
-  for (int o : gl.owner) nl[o]++;
-  const int nlm = nl[P.mev];
-  // ---- the W-set transform of the local fields into a band-sized array [field][band point]
-  StageBuf tband((size_t)nlm * bandp * P.esz), sbuf((size_t)nlm * bandp * P.esz), rbuf((size_t)if_gp_g * myp * P.esz);
-  if ((nlm && (!tband.p || !sbuf.p)) || !rbuf.p) EMI_FAIL(EMI_ERR_RUNTIME, "%s: no device memory for the exchange between the V-sets", who);
-  if (nlm) {
-    in.gp = tband.p, in.gp_nfld = nlm, in.gpuv = in.gp3a = in.gp3b = in.gp2 = nullptr, in.kproma = (int)bandp;
-    const int rc = inv_trans_impl(kresol, &in, adj);
-    if (rc) return rc;
-  }
-  // ---- TRLTOG: block (me -> v') = my fields on the points of sub-band v'
+  in.gp = tband.p, in.gp_nfld = nlm, in.gpuv = in.gp3a = in.gp3b = in.gp2 = nullptr, in.kproma = (int)bandp;
+  // ---- TRLTOG / TRGTOL: one all-to-all-v among the NPRTRV tasks of the band.  The block with V-set v is, on the band side, the
+  // local fields on the points of sub-band v and, on the grid side, the fields of V-set v on this task's points.
   std::vector<StageBuf *> keep;
-  std::vector<long long> sc(P.nprv), rc(P.nprv);
-  std::vector<GridFld> tb(nlm);
-  for (int j = 0; j < nlm; j++) tb[j].base = tband.p, tb[j].nf_arr = nlm, tb[j].fidx = j;
-  int bad = 0;
-  size_t soff = 0;
-  for (int v = 0; v < P.nprv && !bad; v++) {
-    const long long np = P.vpoints(P.me, v);
-    std::vector<GridFld> ds(nlm);
-    for (int j = 0; j < nlm; j++) ds[j] = dense_field((char *)sbuf.p + soff, j, np, P.esz);
-    bad = v_copy(P, tb, ds, P.voffset(v), 0, np, bandp, np, keep, st);
-    sc[v] = (long long)nlm * np * P.esz;
-    rc[v] = (long long)nl[v] * myp * P.esz;
-    soff += (size_t)sc[v];
-  }
-  if (!bad) bad = hook_alltoallv(sbuf.p, sc, rbuf.p, rc, P.nprv, 1, P.me * P.nprv, st);
-  size_t roff = 0;
-  for (int v = 0; v < P.nprv && !bad; v++) {
-    std::vector<GridFld> sr, dd;
-    for (size_t k = 0; k < gl.g.size(); k++)
-      if (gl.owner[k] == v) {
-        sr.push_back(dense_field((char *)rbuf.p + roff, sr.size(), myp, P.esz));
-        dd.push_back(gl.g[k]);
+  std::vector<long long> nbb(P.nprv), ngb(P.nprv);  // bytes of the band-side and grid-side blocks
+  for (int v = 0; v < P.nprv; v++) nbb[v] = (long long)nlm * P.vpoints(P.me, v) * P.esz, ngb[v] = (long long)nl[v] * myp * P.esz;
+  // pack (k_gridcopy into the dense [field][point] blocks at buf) or unpack one side
+  auto copy = [&](bool band, void *buf, bool pack) {
+    size_t off = 0;
+    for (int v = 0; v < P.nprv; v++) {
+      std::vector<GridFld> arr, blk;  // the fields of block v in the band array / the caller's arrays, and in the block
+      long long np = myp, p0 = 0, anp = nproma;  // points of the block; its first point and NPROMA in the arrays
+      if (band) {
+        np = P.vpoints(P.me, v), p0 = P.voffset(v), anp = bandp;
+        for (int j = 0; j < nlm; j++) arr.push_back(GridFld{tband.p, nlm, j, 0, 0});
+      } else {
+        for (size_t k = 0; k < gl.size(); k++)
+          if (owner[k] == v) arr.push_back(gl[k].g);
       }
-    bad = v_copy(P, sr, dd, 0, 0, myp, myp, nproma, keep, st);
-    roff += (size_t)rc[v];
+      for (size_t j = 0; j < arr.size(); j++) blk.push_back(dense_field((char *)buf + off, j, np, P.esz));
+      if (pack ? v_copy(P, arr, blk, p0, 0, np, anp, np, keep, st) : v_copy(P, blk, arr, 0, p0, np, np, anp, keep, st)) return true;
+      off += blk.size() * (size_t)np * P.esz;
+    }
+    return false;
+  };
+  auto trans_v = [&](bool to_grid) {
+    const bool bad = to_grid ? copy(true, xband.p, true) || hook_alltoallv(xband.p, nbb, xgrid.p, ngb, P.nprv, 1, P.me * P.nprv, st) || copy(false, xgrid.p, false)
+                             : copy(false, xgrid.p, true) || hook_alltoallv(xgrid.p, ngb, xband.p, nbb, P.nprv, 1, P.me * P.nprv, st) || copy(true, xband.p, false);
+    return bad ? EMI_ERR_RUNTIME : EMI_SUCCESS;
+  };
+  int rc;
+  if (inverse) {
+    if (nlm && (rc = wset_transform(P, in, true, adj, who)) != EMI_SUCCESS) return rc;
+    rc = trans_v(true);
+  } else {
+    rc = trans_v(false);
+    if (rc == EMI_SUCCESS && nlm) rc = wset_transform(P, in, false, adj, who);
   }
-  if (host && !bad) hs.flush(st);
+  if (host && rc == EMI_SUCCESS) hs.flush(st);
   else emi_stream_sync(st);  // the scratch buffers go back to the pool below
   for (StageBuf *k : keep) delete k;
-  return bad ? EMI_ERR_RUNTIME : EMI_SUCCESS;
-}
-
-static int dir_trans_vsets(int kresol, const emi_dirtrans_t *ap, bool adj, const AdjOpts *ao) {
-  Plan *Pp = get_plan(kresol);
-  const char *who = adj ? "INV_TRANSAD" : "DIR_TRANS";
-  if (!Pp) EMI_FAIL(EMI_ERR_STATE, "%s: unknown resolution %d", who, kresol);
-  if (!ap) EMI_FAIL(EMI_ERR_ARG, "%s: null argument block", who);
-  Plan &P = *Pp;
-  const emi_dirtrans_t &a = *ap;
-  if (ao && (ao->scders || ao->vorgp || ao->divgp || ao->uvder))
-    EMI_FAIL(EMI_ERR_UNSUPPORTED, "INV_TRANSAD: LDSCDERS / LDVORGP / LDDIVGP / LDUVDER are not supported with NPRTRV > 1");
-  emi_stream_t st = (emi_stream_t)a.stream;
-  const bool host = a.mem_space == EMI_MEM_HOST;
-  VGroups vg;
-  if (v_groups(P, a, who, vg)) return EMI_ERR_ARG;
-  const int nuvg = vg.nuv_g, nscg = (int)vg.sc_g.size();
-  const int if_gp_g = 2 * nuvg + nscg;
-  if (if_gp_g == 0) return EMI_SUCCESS;
-  const long long myp = P.vpoints(P.me, P.mev), bandp = P.ngptot;
-  const int nproma = a.kproma > 0 ? a.kproma : (int)myp;
-  const int ngpblks = (int)((myp - 1) / nproma + 1);
-  if (a.gp) {
-    if (a.gpuv || a.gp3a || a.gp3b || a.gp2) EMI_FAIL(EMI_ERR_ARG, "%s:PGP AND PGPUV/PGP3A/PGP3B/PGP2 CAN NOT BOTH BE PRESENT", who);
-    if (a.gp_nfld < if_gp_g) EMI_FAIL(EMI_ERR_ARG, "%s:SECOND DIMENSION OF PGP TOO SMALL (%d < %d)", who, a.gp_nfld, if_gp_g);
-  } else {
-    if (nuvg > 0 && !a.gpuv) EMI_FAIL(EMI_ERR_ARG, "%s:PGPUV MISSING", who);
-    if (vg.nsc_g[0] > 0) EMI_FAIL(EMI_ERR_ARG, "%s:PGP MISSING (PSPSCALAR needs PGP)", who);
-    if (vg.nsc_g[1] > 0 && !a.gp2) EMI_FAIL(EMI_ERR_ARG, "%s:PGP2 MISSING", who);
-    if (vg.nsc_g[2] * vg.nvar3a > 0 && !a.gp3a) EMI_FAIL(EMI_ERR_ARG, "%s:PGP3A MISSING", who);
-    if (vg.nsc_g[3] * vg.nvar3b > 0 && !a.gp3b) EMI_FAIL(EMI_ERR_ARG, "%s:PGP3B MISSING", who);
-  }
-  HostStage hs(P.esz);
-  const size_t ns2 = P.nspec2, gsz = (size_t)nproma * ngpblks;
-  emi_dirtrans_t in = a;
-  in.mem_space = EMI_MEM_DEVICE;
-  in.ext = nullptr;
-  in.vsets = nullptr;
-  in.spvor = hs.out(a.spvor, ns2 * a.nf_uv, host), in.spdiv = hs.out(a.spdiv, ns2 * a.nf_uv, host);
-  in.spscalar = hs.out(a.spscalar, ns2 * a.nf_scalar, host), in.spsc2 = hs.out(a.spsc2, ns2 * a.nf_sc2, host);
-  in.spsc3a = hs.out(a.spsc3a, ns2 * a.sc3a_nlev * a.sc3a_nvar, host), in.spsc3b = hs.out(a.spsc3b, ns2 * a.sc3b_nlev * a.sc3b_nvar, host);
-  void *d_gp = (void *)hs.in(a.gp, gsz * a.gp_nfld, host, st);
-  void *d_gpuv = (void *)hs.in(a.gpuv, gsz * nuvg * 2, host && nuvg, st);
-  void *d_gp2 = (void *)hs.in(a.gp2, gsz * vg.nsc_g[1], host, st);
-  void *d_gp3a = (void *)hs.in(a.gp3a, gsz * vg.nsc_g[2] * vg.nvar3a, host, st);
-  void *d_gp3b = (void *)hs.in(a.gp3b, gsz * vg.nsc_g[3] * vg.nvar3b, host, st);
-  if (hs.failed) EMI_FAIL(EMI_ERR_RUNTIME, "%s: cannot stage the host arrays through device memory (%s)", who, emi_last_error());
-  VGridList gl;  // u(nuv_g) v(nuv_g) scalars: dir_trans.F90:301
-  v_grid_fields(vg, false, false, false, false, d_gp, a.gp_nfld, d_gpuv, 2, d_gp2, d_gp3a, d_gp3b, gl);
-  std::vector<int> nl(P.nprv, 0);
-  for (int o : gl.owner) nl[o]++;
-  const int nlm = nl[P.mev];
-  StageBuf tband((size_t)nlm * bandp * P.esz), rbuf((size_t)nlm * bandp * P.esz), sbuf((size_t)if_gp_g * myp * P.esz);
-  if ((nlm && (!tband.p || !rbuf.p)) || !sbuf.p) EMI_FAIL(EMI_ERR_RUNTIME, "%s: no device memory for the exchange between the V-sets", who);
-  // ---- TRGTOL: block (me -> v'') = the fields of V-set v'' on my points
-  std::vector<StageBuf *> keep;
-  std::vector<long long> sc(P.nprv), rc(P.nprv);
-  int bad = 0;
-  size_t soff = 0;
-  for (int v = 0; v < P.nprv && !bad; v++) {
-    std::vector<GridFld> sr, dd;
-    for (size_t k = 0; k < gl.g.size(); k++)
-      if (gl.owner[k] == v) {
-        dd.push_back(dense_field((char *)sbuf.p + soff, dd.size(), myp, P.esz));
-        sr.push_back(gl.g[k]);
-      }
-    bad = v_copy(P, sr, dd, 0, 0, myp, nproma, myp, keep, st);
-    sc[v] = (long long)nl[v] * myp * P.esz;
-    rc[v] = (long long)nlm * P.vpoints(P.me, v) * P.esz;
-    soff += (size_t)sc[v];
-  }
-  if (!bad) bad = hook_alltoallv(sbuf.p, sc, rbuf.p, rc, P.nprv, 1, P.me * P.nprv, st);
-  std::vector<GridFld> tb(nlm);
-  for (int j = 0; j < nlm; j++) tb[j].base = tband.p, tb[j].nf_arr = nlm, tb[j].fidx = j;
-  size_t roff = 0;
-  for (int v = 0; v < P.nprv && !bad; v++) {
-    const long long np = P.vpoints(P.me, v);
-    std::vector<GridFld> sr(nlm);
-    for (int j = 0; j < nlm; j++) sr[j] = dense_field((char *)rbuf.p + roff, j, np, P.esz);
-    bad = v_copy(P, sr, tb, 0, P.voffset(v), np, np, bandp, keep, st);
-    roff += (size_t)rc[v];
-  }
-  int rcode = bad ? EMI_ERR_RUNTIME : EMI_SUCCESS;
-  if (!bad && nlm) {
-    in.gp = tband.p, in.gp_nfld = nlm, in.gpuv = in.gp3a = in.gp3b = in.gp2 = nullptr, in.kproma = (int)bandp;
-    rcode = dir_trans_impl(kresol, &in, adj, nullptr);
-  }
-  if (host && rcode == EMI_SUCCESS) hs.flush(st);
-  else emi_stream_sync(st);
-  for (StageBuf *k : keep) delete k;
-  return rcode;
+  return rc;
 }
 
 // EMI_MEM_AUTO of a transform call: every array of the argument block is classified (emi_ptr_space); the call then runs as
@@ -3854,19 +3660,24 @@ static int resolve_call(const char *who, const A *ap, A &a) {
   return resolve_space(who, ap->mem_space, {ap->spvor, ap->spdiv, ap->spscalar, ap->spsc3a, ap->spsc3b, ap->spsc2, ap->gp, ap->gpuv, ap->gp3a, ap->gp3b, ap->gp2},
                        &a.mem_space, true);
 }
+// INV_TRANS / DIR_TRANSAD run the inverse pipeline, DIR_TRANS / INV_TRANSAD the direct one
+static int transform(int kresol, const Call &c, bool inverse, bool adj) {
+  const char *who = inverse ? (adj ? "DIR_TRANSAD" : "INV_TRANS") : (adj ? "INV_TRANSAD" : "DIR_TRANS");
+  Plan *Pp = get_plan(kresol);
+  if (!Pp) EMI_FAIL(EMI_ERR_STATE, "%s: unknown resolution %d", who, kresol);
+  return G.nprtrv > 1 ? vset_transform(*Pp, c, inverse, adj, who) : wset_transform(*Pp, c, inverse, adj, who);
+}
 extern "C" int emi_inv_trans(int kresol, const emi_invtrans_t *args) {
   EmiRange rg(EMI_LBL_INV);  // GSTATS 4
   emi_invtrans_t a;
   if (resolve_call("INV_TRANS", args, a)) return EMI_ERR_ARG;
-  if (G.nprtrv > 1) return inv_trans_vsets(kresol, &a, false);
-  return inv_trans_impl(kresol, &a, false);
+  return transform(kresol, to_call(a), true, false);
 }
 extern "C" int emi_dir_trans(int kresol, const emi_dirtrans_t *args) {
   EmiRange rg(EMI_LBL_DIR);  // GSTATS 5
   emi_dirtrans_t a;
   if (resolve_call("DIR_TRANS", args, a)) return EMI_ERR_ARG;
-  if (G.nprtrv > 1) return dir_trans_vsets(kresol, &a, false, nullptr);
-  return dir_trans_impl(kresol, &a, false);
+  return transform(kresol, to_call(a), false, false);
 }
 extern "C" int emi_wait(int kresol) {
   if (!G.init) EMI_FAIL(EMI_ERR_STATE, "emi_wait: SETUP_TRANS0 has not been called");
@@ -3884,48 +3695,19 @@ extern "C" int emi_wait(int kresol) {
   return EMI_SUCCESS;
 }
 
-// INV_TRANSAD (include/ectrans/inv_transad.h): arguments of INV_TRANS with the intents swapped
+// INV_TRANSAD (include/ectrans/inv_transad.h): arguments of INV_TRANS with the intents swapped.  LDSCDERS / LDVORGP / LDDIVGP /
+// LDUVDER: the grid arrays then carry the derivative / vorticity / divergence inputs in INV_TRANS's layout (ltinvad_mod.F90:149-225,
+// spnsdead_mod.F90, fscad_mod.F90)
 extern "C" int emi_inv_transad(int kresol, const emi_invtrans_t *ap) {
   emi_invtrans_t a;
   if (resolve_call("INV_TRANSAD", ap, a)) return EMI_ERR_ARG;
-  emi_dirtrans_t d{};
-  d.mem_space = a.mem_space;
-  d.spvor = (void *)a.spvor, d.spdiv = (void *)a.spdiv, d.nf_uv = a.nf_uv;
-  d.spscalar = (void *)a.spscalar, d.nf_scalar = a.nf_scalar;
-  d.spsc3a = (void *)a.spsc3a, d.sc3a_nlev = a.sc3a_nlev, d.sc3a_nvar = a.sc3a_nvar;
-  d.spsc3b = (void *)a.spsc3b, d.sc3b_nlev = a.sc3b_nlev, d.sc3b_nvar = a.sc3b_nvar;
-  d.spsc2 = (void *)a.spsc2, d.nf_sc2 = a.nf_sc2;
-  d.kproma = a.kproma;
-  d.gp = a.gp, d.gp_nfld = a.gp_nfld, d.gpuv = a.gpuv, d.gp3a = a.gp3a, d.gp3b = a.gp3b, d.gp2 = a.gp2;
-  d.stream = a.stream;
-  d.ext = a.ext;
-  d.vsets = a.vsets;
-  // LDSCDERS / LDVORGP / LDDIVGP / LDUVDER: the grid arrays then carry the derivative / vorticity / divergence inputs in
-  // INV_TRANS's layout (ltinvad_mod.F90:149-225, spnsdead_mod.F90, fscad_mod.F90)
-  AdjOpts ao;
-  ao.scders = a.ldscders != 0, ao.vorgp = a.ldvorgp != 0, ao.divgp = a.lddivgp != 0 || a.ldvorgp != 0, ao.uvder = a.lduvder != 0;
-  if (G.nprtrv > 1) return dir_trans_vsets(kresol, &d, true, &ao);
-  return dir_trans_impl(kresol, &d, true, &ao);
+  return transform(kresol, to_call(a), false, true);
 }
 // DIR_TRANSAD (include/ectrans/dir_transad.h): arguments of DIR_TRANS with the intents swapped
 extern "C" int emi_dir_transad(int kresol, const emi_dirtrans_t *ap) {
   emi_dirtrans_t d;
   if (resolve_call("DIR_TRANSAD", ap, d)) return EMI_ERR_ARG;
-  emi_invtrans_t a{};
-  a.mem_space = d.mem_space;
-  a.spvor = d.spvor, a.spdiv = d.spdiv, a.nf_uv = d.nf_uv;
-  a.spscalar = d.spscalar, a.nf_scalar = d.nf_scalar;
-  a.spsc3a = d.spsc3a, a.sc3a_nlev = d.sc3a_nlev, a.sc3a_nvar = d.sc3a_nvar;
-  a.spsc3b = d.spsc3b, a.sc3b_nlev = d.sc3b_nlev, a.sc3b_nvar = d.sc3b_nvar;
-  a.spsc2 = d.spsc2, a.nf_sc2 = d.nf_sc2;
-  a.kproma = d.kproma;
-  a.gp = (void *)d.gp, a.gp_nfld = d.gp_nfld, a.gpuv = (void *)d.gpuv, a.gp3a = (void *)d.gp3a, a.gp3b = (void *)d.gp3b,
-  a.gp2 = (void *)d.gp2;
-  a.stream = d.stream;
-  a.ext = d.ext;
-  a.vsets = d.vsets;
-  if (G.nprtrv > 1) return inv_trans_vsets(kresol, &a, true);
-  return inv_trans_impl(kresol, &a, true);
+  return transform(kresol, to_call(d), true, true);
 }
 
 #if defined(EMI_MR_STAMP) && !defined(EMI_CPU_EMU)

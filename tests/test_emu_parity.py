@@ -350,6 +350,18 @@ def test_argument_errors_mirror_abort_trans(et):
         et.inv_trans(r, pspscalar=np.zeros((ns2, 1)), pspsc2=np.zeros((ns2, 1)), pgp=np.zeros((1, 2, ng)))
     with pytest.raises(et.TransError, match="unknown resolution"):
         et.inv_trans(r + 1, pspscalar=np.zeros((ns2, 1)), pgp=np.zeros((1, 1, ng)))
+    # the same checks through every entry point, each with its own name in front
+    z = np.zeros
+    for fn, who in ((et.inv_trans, "INV_TRANS"), (et.dir_trans, "DIR_TRANS"), (et.inv_transad, "INV_TRANSAD"),
+                    (et.dir_transad, "DIR_TRANSAD")):
+        with pytest.raises(et.TransError, match="^%s : PSPSCALAR AND PSPSC3A/PSPSC3B/PSPSC2 BOTH PRESENT" % who):
+            fn(r, pspscalar=z((ns2, 1)), pspsc2=z((ns2, 1)), pgp=z((1, 2, ng)))
+        with pytest.raises(et.TransError, match="^%s:PGP AND PGPUV/PGP3A/PGP3B/PGP2 CAN NOT BOTH BE PRESENT" % who):
+            fn(r, pspscalar=z((ns2, 1)), pgp=z((1, 1, ng)), pgp2=z((1, 1, ng)))
+        with pytest.raises(et.TransError, match=r"^%s:SECOND DIMENSION OF PGP TOO SMALL \(2 < 3\)" % who):
+            fn(r, pspscalar=z((ns2, 3)), pgp=z((1, 2, ng)))
+        with pytest.raises(et.TransError, match="^%s:PGP3A MISSING" % who):
+            fn(r, pspsc3a=z((2, ns2, 3)))
     et.trans_release(r)
     with pytest.raises(et.TransError, match="unknown resolution"):
         et.trans_inq(r, "nspec2")
