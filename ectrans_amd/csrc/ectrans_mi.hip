@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -206,9 +207,35 @@ template <class T>
 static int upload(const std::vector<T> &h, T **d) {
   void *p = nullptr;
   if (emi_dev_malloc(&p, h.size() * sizeof(T))) return -1;
-  if (!h.empty() && emi_h2d(p, h.data(), h.size() * sizeof(T), 0)) return -1;
-  if (emi_stream_sync(0)) return -1;  // the host vector may die right after this call
+  if ((!h.empty() && emi_h2d(p, h.data(), h.size() * sizeof(T), 0)) || emi_stream_sync(0)) {  // (the wait: the host vector may die right after this call)
+    emi_dev_free(p);
+    return -1;
+  }
   *d = (T *)p;
+  return 0;
+}
+// Device allocations with one owner that frees them: a plan, for its tables, or a stage of SETUP_TRANS, for its temporaries.
+struct DevAllocs {
+  std::vector<void *> list;
+  DevAllocs() = default;
+  DevAllocs(const DevAllocs &) = delete;
+  DevAllocs &operator=(const DevAllocs &) = delete;
+  ~DevAllocs() {
+    for (void *p : list) emi_dev_free(p);
+  }
+  int alloc(void **p, size_t bytes) {
+    if (emi_dev_malloc(p, bytes)) return -1;
+    list.push_back(*p);
+    return 0;
+  }
+};
+// a host table to the device, entered with its owner and assigned to the field that names it
+template <class T, class F>
+static int upload(DevAllocs &owner, const std::vector<T> &h, F *field) {
+  T *d = nullptr;
+  if (upload(h, &d)) return -1;
+  owner.list.push_back(d);
+  *field = d;
   return 0;
 }
 
@@ -247,13 +274,16 @@ struct FftClass {  // one launch group of the FFT kernels: latitudes sharing a w
 // blocks and the Legendre-panel row blocks of one m in its 4 MiB L2, instead of streaming 26 different
 // column blocks per row tile (measured: 13x the algorithmic HBM bytes).  Tiles stay m-ascending
 // (longest K first) within every XCD, so all XCDs progress through m together.
-struct LegMaps {
+struct LegMaps {  // (the maps are the plan's allocations, like every table)
   int2 *d_inv = nullptr, *d_dir = nullptr, *d_inv_wide = nullptr, *d_dir_wide = nullptr;  // *_wide: fp32 library, the tiles of zonal wavenumber 0 (k_leg_*_wide)
   long long n_inv = 0, n_dir = 0, n_inv_wide = 0, n_dir_wide = 0;
 };
 
-struct Plan {
-  bool active = false;
+struct Plan {  // owns its device memory; whoever drops a plan that has run something waits for the device first (emi_release)
+  Plan() = default;
+  Plan(const Plan &) = delete;
+  Plan &operator=(const Plan &) = delete;
+  ~Plan();
   int nsmax = 0, ndgl = 0, ndgnh = 0;
   bool reduced = false;
   double ra = 6371229.0;
@@ -291,7 +321,7 @@ struct Plan {
   std::vector<long long> leg_rows, leg_disp, fft_rows, fft_disp;  // [nproc]
   // device
   EmiGeomDev g{};
-  std::vector<void *> dev_allocs;
+  DevAllocs dev_allocs;  // the panels and every table, the Legendre tile maps included
   int esz = 8;  // bytes per real: 8 (fp64 library, the reference's _dp build) or 4 (fp32, _sp)
   char *d_P = nullptr, *d_PT = nullptr;  // esz-sized reals
   // fft
@@ -315,6 +345,17 @@ struct Plan {
 #endif
   bool ev_valid = false;
 };
+
+Plan::~Plan() {
+#ifndef EMI_CPU_EMU
+  if (ev_done) (void)hipEventDestroy(ev_done);
+#endif
+  emi_dev_free(d_W);
+  emi_dev_free(d_FBL);
+  if (d_FBF != d_FBL) emi_dev_free(d_FBF);
+  emi_dev_free(d_desc);
+  emi_dev_free(d_fftscr);
+}
 
 static int roundup(int a, int b) { return (a + b - 1) / b * b; }
 // EMI_TEST_PATHS (tests only; read at every SETUP_TRANS / call, so a test can flip it): bit 0 = exchange-order row tables on ONE task
@@ -382,7 +423,7 @@ static struct {
   // NPRTRV > 1 (sump_trans0_mod.F90:49, pe2set_mod.F90:111-112): nproc_all = NPRTRW x NPRTRV tasks; task myproc_all is
   // (MYSETW, MYSETV) = ((myproc_all - 1) / NPRTRV + 1, mod(myproc_all - 1, NPRTRV) + 1); the tasks of a W-set are neighbours
   int nproc_all = 1, myproc_all = 1, nprtrv = 1, mysetv = 1, nprtrv_preset = 0;
-  std::vector<Plan *> plans;
+  std::vector<std::unique_ptr<Plan>> plans;  // [max_resol] a slot holds a plan from the end of its SETUP_TRANS to its TRANS_RELEASE
   int max_batch = 0;
   int profile = 0;  // 1: phase timers per call; 2: accumulated over the calls since emi_set_profile(2)
   emi_alltoallv_fn a2a = nullptr;
@@ -393,8 +434,8 @@ static struct {
 } G;
 
 static Plan *get_plan(int kresol) {
-  if (!G.init || kresol < 1 || kresol > (int)G.plans.size() || !G.plans[kresol - 1] || !G.plans[kresol - 1]->active) return nullptr;
-  return G.plans[kresol - 1];
+  if (!G.init || kresol < 1 || kresol > (int)G.plans.size()) return nullptr;
+  return G.plans[kresol - 1].get();
 }
 
 extern "C" int emi_set_nprtrv(int nprtrv) {
@@ -425,7 +466,8 @@ extern "C" int emi_init(const emi_init_t *cfg) {
     EMI_FAIL(EMI_ERR_RUNTIME, "emi_init: no HIP device visible -- libectrans_mi has no CPU path");
   if (c.device >= 0) EMI_CHECK(hipSetDevice(c.device));
 #endif
-  G.plans.assign(G.max_resol, nullptr);
+  G.plans.clear();
+  G.plans.resize(G.max_resol);
   const char *pe = getenv("EMI_PROFILE");
   G.profile = pe ? atoi(pe) : 0;
   const char *mb = getenv("EMI_MAX_BATCH");
@@ -505,343 +547,349 @@ static bool mr_choose(int sz, int esz, int fac[3], int &fbk, int &nthr) {
   return found;
 }
 
+// ---- the FFT policy: which kernel family runs a row of length n, and how.  fft_choose decides; build_fft_plans keeps the books.
+struct FftSwitches {  // read once per SETUP_TRANS (tests flip them between setups)
+  bool mr, r16, r16s, hot;
+  static bool off(const char *name) { return getenv(name) && atoi(getenv(name)) == 0; }
+  FftSwitches() : mr(!off("EMI_FFT_MR")), r16(!off("EMI_FFT_R16")), r16s(!off("EMI_FFT_R16S")), hot(!getenv("EMI_FFT_NO_HOT")) {}
+};
+struct HotPlan {  // one row of EMI_HOT_PLAN_LIST: kernel id, work length, factor list, fields per workgroup (of the fp64 library)
+  int pc, S, nfac, fac[5], nfl;
+};
+static const HotPlan g_hot_plans[] = {
+#define EMI_HOT_ROW(pc_, S_, nf_, a_, b_, c_, d_, e_, nfl_) {pc_, S_, nf_, {a_, b_, c_, d_, e_}, nfl_},
+    EMI_HOT_PLAN_LIST(EMI_HOT_ROW)
+#undef EMI_HOT_ROW
+};
+#define EMI_LIST_ROW(r_) r_,
+static const int g_r16_list[] = {EMI_R16_LIST(EMI_LIST_ROW)}, g_r16s_list[] = {EMI_R16S_LIST(EMI_LIST_ROW)};
+#undef EMI_LIST_ROW
+
+// fields per workgroup of the in-place LDS kernels: as many as fit ~40 KiB of LDS (power of two, <= 16); longer rows get one
+// field per workgroup and more threads
+static int fft_fields_40k(size_t per_field) {
+  int fbk = 16;
+  while (fbk > 1 && fbk * per_field > 40960) fbk >>= 1;
+  return fbk;
+}
+// Threads per workgroup follow the LDS footprint: 256 up to
+// 40 KiB, 512 up to 80 KiB, else 1024 -- i.e. always 16 waves per CU at 128 VGPRs.  (One thread per
+// radix-8 butterfly, S/8, removes the idle lanes of the second sweep at S = 2560/3072/4608/5120
+// but makes workgroups of 5, 9 and 10 waves, of which only one fits the 16-wave budget: measured
+// 25 % slower.)
+static int fft_threads(size_t lds_bytes) { return lds_bytes <= 40960 ? 256 : (lds_bytes <= 81920 ? 512 : 1024); }
+
+struct FftChoice {
+  FftPlanDev pl{};  // n, cmode, sz, blue, mr, r16, split, S, nfac, fac, fbk decided; offsets and launch class are the caller's
+  int nthr = 0;     // threads per workgroup (fields per workgroup: pl.fbk)
+  int hot = 0;      // > 0: k_fft_*_hot<hot>
+  bool gmem = false;  // the work array does not fit the LDS: k_fft_*_gm on a global scratch buffer
+};
+static int fft_choose(int n, int esz, const FftSwitches &sw, FftChoice &c) {
+  FftPlanDev &pl = c.pl;
+  pl.n = n;
+  pl.cmode = (n % 2 != 0);
+  pl.sz = pl.cmode ? n : n / 2;
+  std::vector<int> fac;
+  pl.blue = !emi::factorize_smooth(pl.sz, fac);
+  pl.S = pl.sz;
+  // Register-resident kernels (k_fft_*_r16<R1>, round 3): rows of even length whose Bluestein work length fits 256 R1, R1 from
+  // EMI_R16_LIST and at least 8 -- at TCo1279 every row of 1540 to 4098 points.  EMI_FFT_R16=0 keeps the in-place LDS kernels (the
+  // tests run the same rows through both families).
+  // Rows of that range with a 7-smooth half-length take them too: per
+  // point the generic kernels cost 8.7 ps and row, the convolution 5.5 - 6 ps per work point (profiles/r3c_pmc_fft.txt), although it
+  // does four times the arithmetic -- every one of those 100-odd row lengths has its own factor list, which the generic kernels
+  // walk at run time.
+  // Direct mixed-radix kernels (k_fft_*_mr, round 3): even rows whose half-length is a product of at most three radices of
+  // EMI_MR_RADICES -- no convolution.  EMI_FFT_MR=0: off (tests: the same rows through the convolution kernels).
+  int mr_fbk = 0, mr_nthr = 0, mr_fac[3] = {1, 1, 1};
+  if (!pl.cmode && pl.sz >= 2 && sw.mr) pl.mr = mr_choose(pl.sz, esz, mr_fac, mr_fbk, mr_nthr) ? 1 : 0;
+  if (pl.mr) {
+    pl.blue = 0;
+    fac.assign(mr_fac, mr_fac + 3);
+  }
+  if (!pl.mr && !pl.cmode && sw.r16) {
+    const int need = 2 * pl.sz - 1;
+    if (need > 1536)  // shorter rows: in-place kernels with several fields per workgroup
+      for (int r : g_r16_list)
+        if (!pl.r16 && 256 * r >= need) pl.r16 = r;
+    // Split kernels (k_fft_*_r16p<R1>, round 6): a row too long for one register-resident convolution whose half-length is even runs as
+    // two convolutions of length sz / 2, one after the other, joined by one decimation step (emi_kernels_body.h).  TCo1279 fp64: 44.6
+    // against 48.2 ms per pair for the rows of k_fft_*_hot<23 | 24>; TCo2559 fp32: the rows of 4100 .. 8192 points 192 against 249 ms per
+    // pair (profiles/r6_fft_experiments.txt).  EMI_FFT_R16S=0: off (tests and A/B runs: the same rows through the in-place LDS kernels).
+    if (!pl.r16 && need > 4096 && pl.sz % 2 == 0 && sw.r16s)
+      for (int r : g_r16s_list)
+        if (!pl.r16 && 256 * r >= pl.sz - 1) pl.r16 = r, pl.split = 2;
+    if (pl.r16) pl.blue = 1;
+  }
+  if (pl.r16) {
+    pl.S = 256 * pl.r16;
+    fac.assign(1, pl.r16);  // bookkeeping only: the factor list of these kernels is R1, 16, 16 at compile time
+  } else if (pl.blue) {
+    pl.S = emi::next_235(2 * pl.sz - 1);
+    emi::factorize_smooth(pl.S, fac);
+    // Specialised kernels (EMI_HOT_PLAN_LIST): the work length and factor list of the cheapest one that is long
+    // enough -- cost model S x (passes + 1), as next_235 -- replace the generic choice when they cost no more: that
+    // covers the merged tails (8, 8, 8, 6 | 9 | 10: one LDS round trip fewer than 8, 8, 8, 2, 3 ...) and any work length of the
+    // list that is not of the form 2^a {1,3,5,9,15} (there are none at present, see emi_types.h).
+    // Even NLOEN only: odd rows run the generic kernels, which have no composite butterflies.  The plan must be the
+    // one for the fields-per-workgroup this work length gets (the 40-KiB rule).
+    if (!pl.cmode && sw.hot) {
+      long long best = (long long)pl.S * (long long)(fac.size() + 1);
+      const HotPlan *pick = nullptr;
+      for (const HotPlan &r : g_hot_plans) {
+        if (r.S < 2 * pl.sz - 1) continue;
+        if (fft_fields_40k((size_t)FFT_LDS_ELEMS(r.S) * 2 * esz) < r.nfl) continue;  // (the fp32 library has room for twice the fields: it runs the plan with the list's count, below)
+        const long long cost = (long long)r.S * (r.nfac + 1);
+        if (cost <= best) {  // list order: a merged tail (ids 22-27) comes after the plain list of its length
+          best = cost;
+          pick = &r;
+        }
+      }
+      if (pick) {
+        pl.S = pick->S;
+        fac.assign(pick->fac, pick->fac + pick->nfac);
+      }
+    }
+  }
+  if (pl.S > 65535 || fac.size() > 14) EMI_FAIL(EMI_ERR_UNSUPPORTED, "FFT length %d not supported (work size %d)", n, pl.S);
+  pl.nfac = (int)fac.size();
+  for (int i = 0; i < pl.nfac; i++) pl.fac[i] = fac[i];
+  const size_t per_field = (size_t)FFT_LDS_ELEMS(pl.S) * 2 * esz;
+  pl.fbk = fft_fields_40k(per_field);
+  // a row whose work array exceeds the 160 KiB of LDS (fp64: more than 10240 complex points -- the four longest rows of
+  // TCo2559, or any caller grid: the reference takes any KLOEN, ftdir_mod.F90:67-84) runs the same passes on a slice
+  // of a global scratch buffer (k_fft_*_gm): slow per row, but such rows are few
+  c.gmem = pl.fbk * per_field > 160 * 1024 && !pl.mr;
+  c.nthr = fft_threads(pl.fbk * per_field);
+  if (pl.r16) {  // one field per workgroup, 256 or 320 threads, one plane + the 240 small twiddles of LDS
+    pl.fbk = 1;
+    c.nthr = 16 * pl.r16 > 256 ? roundup(16 * pl.r16, 64) : 256;
+  } else if (pl.mr) {
+    pl.fbk = mr_fbk;
+    c.nthr = mr_nthr;
+  } else if (pl.blue && !pl.cmode && !c.gmem && sw.hot) {
+    // specialised kernel for this work length and factor list?
+    // The list's fields-per-workgroup are those of the fp64 library.  The fp32 library could hold twice as many in its 40 KiB, for which no
+    // kernel is compiled: until round 6 its short rows (work lengths <= 1536) therefore fell through to the generic kernels -- 14.7 of the
+    // 117 ms of FFT per pair at TCo1279 (profiles/r6_pmc_fft_fp32.txt: k_fft_dir 8.35 + k_fft_inv 6.32 ms).  They take the list's plan with
+    // the list's field count now (half the LDS per workgroup; the wave budget of the CU is what limits both).
+    int hot_fbk = 0;
+    for (const HotPlan &r : g_hot_plans)
+      if (r.S == pl.S && r.nfac == pl.nfac && r.nfl <= pl.fbk && std::equal(r.fac, r.fac + r.nfac, pl.fac)) c.hot = r.pc, hot_fbk = r.nfl;
+    if (c.hot) {
+      pl.fbk = hot_fbk;
+      c.nthr = fft_threads(pl.fbk * per_field);  // = hot_threads(pc): what the specialised kernels are compiled for
+    }
+  }
+  for (int i = 0; i < pl.nfac; i++)
+    if (!c.hot && !pl.r16 && !pl.mr && (pl.fac[i] == 6 || pl.fac[i] > 8)) EMI_FAIL(EMI_ERR_RUNTIME, "internal: composite FFT radix %d without a specialised kernel (length %d)", pl.fac[i], n);
+  return 0;
+}
+
+// Work sizes share their tables: the twiddle tables and
+// the digit-reversal table depend only on the work size S and its factor list, so all plans with the
+// same S share one copy (TCo1279: ~20 work sizes for 1280 row lengths -- 2 MB of twiddles that stay in
+// L2 instead of 130 MB); the real-pack twiddles, the chirp and the filter spectrum are per length.
+struct FftShared {
+  int S, tw_off, perm_off, ptw_off[14];
+  std::vector<int> fac;
+  int r16 = 0, mr = 0;
+};
+struct FftTabSizes { size_t tw = 0, ptw = 0, perm = 0, rtw = 0, chirp = 0, bhat = 0; };
+
+// the tables of one work size: tw, ptw, perm at the offsets of `sh`
+static void fft_fill_shared(const FftShared &sh, std::vector<d2> &tw, std::vector<d2> &ptw, std::vector<uint16_t> &perm) {
+  const int S = sh.S;
+  if (sh.mr) {
+    const int A = sh.fac[0], B = sh.fac[1], C = sh.fac[2], P1 = (B * C) | 1;
+    auto w = [&](long long e) {
+      long double a = 2.0L * (long double)M_PIl * (long double)(e % S) / (long double)S;
+      return d2{(double)cosl(a), (double)-sinl(a)};
+    };
+    d2 *t1 = ptw.data() + sh.ptw_off[0], *t2 = ptw.data() + sh.ptw_off[1];
+    for (int k1 = 0; k1 < A; k1++) t1[k1] = w((long long)C * k1);
+    for (int q = 0; q < A * B; q++) t2[q] = w((long long)q);
+    for (int k = 0; k < S; k++) perm[sh.perm_off + k] = (uint16_t)((k % A) * P1 + ((k / A) % B) * C + k / (A * B));
+    return;
+  }
+  if (sh.r16) {
+    d2 *dst = ptw.data() + sh.ptw_off[0];
+    for (int row = 0; row < 7; row++) {
+      const int mult = row < 3 ? row + 1 : 4 * (row - 2);
+      for (int t = 0; t < 256; t++) {
+        long double a = 2.0L * (long double)M_PIl * (long double)(((long long)t * mult) % S) / (long double)S;
+        *dst++ = d2{(double)cosl(a), (double)-sinl(a)};
+      }
+    }
+    return;
+  }
+  for (int k = 0; k < S; k++) {
+    long double a = 2.0L * (long double)M_PIl * (long double)k / (long double)S;
+    tw[sh.tw_off + k] = d2{(double)cosl(a), (double)-sinl(a)};
+  }
+  // per-pass twiddle tables, [t-1][j] with j fastest (coalesced reads)
+  long long lenp = 1;
+  for (size_t ip = 0; ip < sh.fac.size(); ip++) {
+    const int R = sh.fac[ip];
+    d2 *dst = ptw.data() + sh.ptw_off[ip];
+    if (lenp > 1)
+      for (int t = 1; t < R; t++)
+        for (long long j = 0; j < lenp; j++) {
+          long double a = 2.0L * (long double)M_PIl * (long double)((j * t) % (lenp * R)) / (long double)(lenp * R);
+          *dst++ = d2{(double)cosl(a), (double)-sinl(a)};
+        }
+    lenp *= R;
+  }
+  std::vector<uint16_t> pm;
+  emi::dit_positions(S, sh.fac, pm);
+  std::copy(pm.begin(), pm.end(), perm.begin() + sh.perm_off);
+}
+
+// the tables of one row length: rtw, chirp, bhat at the offsets of `pl` (perm: filled before)
+static void fft_fill_length(const FftPlanDev &pl, const std::vector<uint16_t> &perm, std::vector<d2> &rtw, std::vector<d2> &chirp, std::vector<d2> &bhat) {
+  const int n = pl.n;
+  const double tpi = 2.0 * M_PI;
+  for (int k = 0; k <= pl.sz; k++) {
+    double a = tpi * (double)k / (double)n;
+    rtw[pl.rtw_off + k] = d2{std::cos(a), -std::sin(a)};
+  }
+  if (!pl.blue) return;
+  d2 *c = chirp.data() + pl.chirp_off;
+  const int csz = pl.split ? pl.sz / 2 : pl.sz;  // length of the chirp-z transform(s) of the row: the split kernels run two of sz / 2
+  for (int k = 0; k < csz; k++) {
+    long long k2 = ((long long)k * k) % (2LL * csz);
+    double a = M_PI * (double)k2 / (double)csz;
+    c[k] = d2{std::cos(a), -std::sin(a)};  // exp(-i pi k^2/csz)
+  }
+  // filter b_j = conj(c_|j|) wrapped to length L; Bhat = DFT_L(b) (direct O(L*sz) sum in
+  // long double: setup only, keeps the table accurate to ~1e-17), stored at the DIT positions
+  const int L = pl.S, r0 = pl.fac[0];
+  const uint16_t *pm = pl.r16 ? nullptr : perm.data() + pl.perm_off;
+  std::vector<long double> cr(L);
+  for (int k = 0; k < L; k++) cr[k] = cosl(2.0L * (long double)M_PIl * (long double)k / (long double)L);
+  d2 *bh = bhat.data() + pl.bhat_off;
+  for (int k = 0; k < L; k++) {
+    long double sr = c[0].x, si = -c[0].y;
+    long long jk = 0;
+    for (int jj = 1; jj < csz; jj++) {
+      // b_j + b_{L-j} term: conj(c_j) * (w^{jk} + w^{-jk}) = conj(c_j) * 2 cos(2 pi j k/L)
+      jk += k;
+      if (jk >= L) jk -= L;
+      long double cs = 2.0L * cr[jk];
+      sr += (long double)c[jj].x * cs;
+      si += -(long double)c[jj].y * cs;
+    }
+    // position p = pm[k] of the DIT-ordered spectrum belongs to the middle butterfly q = p / R0 as its
+    // element t = p % R0; stored [t][q] so that a wave reads its filter values coalesced
+    if (pl.r16) {
+      // k = k0 + R1 (k1 + 16 k2) sits in register k2 of thread 16 k0 + k1 of the fused middle pass: table [k2][16 k0 + k1]
+      const int k0 = k % pl.r16, kk = k / pl.r16, k1 = kk % 16, k2 = kk / 16;
+      bh[(size_t)k2 * (16 * pl.r16) + 16 * k0 + k1] = d2{(double)(sr / (long double)L), (double)(si / (long double)L)};  // the 1/S of the convolution folded in
+      continue;
+    }
+    const int p = pm[k];
+    bh[(size_t)(p % r0) * (L / r0) + p / r0] = d2{(double)sr, (double)si};
+  }
+}
+
+// the shared tables of a new plan: found, or entered with their offsets
+static const FftShared &fft_share_tables(const FftPlanDev &pl, std::map<int, int> &sidx, std::vector<FftShared> &shared, FftTabSizes &n) {
+  const int skey = pl.S * 16 + (pl.r16 ? 15 : (pl.mr ? 14 : pl.nfac));  // the tables depend on the factor list: merged and plain lists differ in length
+  auto si = sidx.find(skey);
+  if (si != sidx.end()) return shared[si->second];
+  FftShared sh{};
+  sh.S = pl.S;
+  sh.fac.assign(pl.fac, pl.fac + pl.nfac);
+  sh.r16 = pl.r16;
+  sh.mr = pl.mr;
+  sh.tw_off = (int)n.tw;
+  sh.perm_off = (int)n.perm;
+  if (pl.mr) {
+    // twiddle bases of pass 2, [k1]: w^(C k1), and of pass 3, [k1 + A k2]: w^(k1 + A k2) (input r of a butterfly times base^r);
+    // perm[k] = LDS position of coefficient k
+    const int A = pl.fac[0], B = pl.fac[1];
+    sh.ptw_off[0] = (int)n.ptw;
+    n.ptw += (size_t)A;
+    sh.ptw_off[1] = (int)n.ptw;
+    n.ptw += (size_t)A * B;
+    sh.ptw_off[2] = (int)n.ptw;
+    n.perm += pl.S;
+  } else if (pl.r16) {
+    // the digit twiddles of A1 / B1: rows 0..2 = w^(t qa), qa = 1..3; rows 3..6 = w^(4 t qb), qb = 1..4; w = exp(-2 pi i / S), t < 256
+    sh.ptw_off[0] = (int)n.ptw;
+    n.ptw += 7 * 256;
+  } else {
+    n.tw += pl.S;
+    n.perm += pl.S;
+    long long lenp = 1;
+    for (int ip = 0; ip < pl.nfac; ip++) {
+      sh.ptw_off[ip] = (int)n.ptw;
+      if (lenp > 1) n.ptw += (size_t)(pl.fac[ip] - 1) * lenp;
+      lenp *= pl.fac[ip];
+    }
+  }
+  sidx.emplace(skey, (int)shared.size());
+  shared.push_back(sh);
+  return shared.back();
+}
+
 static int build_fft_plans(Plan &P) {
-  // Pass 1 (serial, cheap): one plan per distinct row length; table offsets.  The twiddle tables and
-  // the digit-reversal table depend only on the work size S and its factor list, so all plans with the
-  // same S share one copy (TCo1279: ~20 work sizes for 1280 row lengths -- 2 MB of twiddles that stay in
-  // L2 instead of 130 MB); the real-pack twiddles, the chirp and the filter spectrum are per length.
+  // Pass 1 (serial, cheap): one plan per distinct row length (fft_choose); table offsets; launch classes.
   // Pass 2 fills the tables on the host threads, one task per table.
-  struct Shared {
-    int S, tw_off, perm_off, ptw_off[14];
-    std::vector<int> fac;
-    int r16 = 0, mr = 0;
-  };
+  const FftSwitches sw;
   std::map<int, int> idx;            // row length -> plan
   std::map<int, int> sidx;           // work size -> shared tables
-  std::vector<Shared> shared;
-  size_t n_tw = 0, n_ptw = 0, n_perm = 0, n_rtw = 0, n_chirp = 0, n_bhat = 0;
+  std::vector<FftShared> shared;
+  FftTabSizes nt;
   P.planid.assign(P.nlat, 0);
   for (int j = 0; j < P.nlat; j++) {  // local latitudes
-    int n = P.nloen[P.lat0 + j];
+    const int n = P.nloen[P.lat0 + j];
     auto it = idx.find(n);
     if (it != idx.end()) {
       P.planid[j] = it->second;
       continue;
     }
-    FftPlanDev pl{};
-    pl.n = n;
-    pl.cmode = (n % 2 != 0);
-    pl.sz = pl.cmode ? n : n / 2;
-    std::vector<int> fac;
-    pl.blue = !emi::factorize_smooth(pl.sz, fac);
-    pl.S = pl.sz;
-    // Register-resident kernels (k_fft_*_r16<R1>, round 3): rows of even length whose Bluestein work length fits 256 R1, R1 from
-    // EMI_R16_LIST and at least 8 -- at TCo1279 every row of 1540 to 4098 points.  EMI_FFT_R16=0 keeps the in-place LDS kernels (the
-    // tests run the same rows through both families).
-    // Rows of that range with a 7-smooth half-length take them too: per
-    // point the generic kernels cost 8.7 ps and row, the convolution 5.5 - 6 ps per work point (profiles/r3c_pmc_fft.txt), although it
-    // does four times the arithmetic -- every one of those 100-odd row lengths has its own factor list, which the generic kernels
-    // walk at run time.
-    // Direct mixed-radix kernels (k_fft_*_mr, round 3): even rows whose half-length is a product of at most three radices of
-    // EMI_MR_RADICES -- no convolution.  EMI_FFT_MR=0: off (tests: the same rows through the convolution kernels).
-    int mr_fbk = 0, mr_nthr = 0, mr_fac[3] = {1, 1, 1};
-    if (!pl.cmode && pl.sz >= 2 && !(getenv("EMI_FFT_MR") && atoi(getenv("EMI_FFT_MR")) == 0))
-      pl.mr = mr_choose(pl.sz, P.esz, mr_fac, mr_fbk, mr_nthr) ? 1 : 0;
-    if (pl.mr) {
-      pl.blue = 0;
-      fac.assign(mr_fac, mr_fac + 3);
-    }
-    if (!pl.mr && !pl.cmode && !(getenv("EMI_FFT_R16") && atoi(getenv("EMI_FFT_R16")) == 0)) {
-      static const int r1s[] = {
-#define EMI_R16_ROW(r_) r_,
-          EMI_R16_LIST(EMI_R16_ROW)
-#undef EMI_R16_ROW
-      };
-      const int need = 2 * pl.sz - 1;
-      if (need > 1536)  // shorter rows: in-place kernels with several fields per workgroup
-        for (int r : r1s)
-          if (!pl.r16 && 256 * r >= need) pl.r16 = r;
-      // Split kernels (k_fft_*_r16p<R1>, round 6): a row too long for one register-resident convolution whose half-length is even runs as
-      // two convolutions of length sz / 2, one after the other, joined by one decimation step (emi_kernels_body.h).  TCo1279 fp64: 44.6
-      // against 48.2 ms per pair for the rows of k_fft_*_hot<23 | 24>; TCo2559 fp32: the rows of 4100 .. 8192 points 192 against 249 ms per
-      // pair (profiles/r6_fft_experiments.txt).  EMI_FFT_R16S=0: off (tests and A/B runs: the same rows through the in-place LDS kernels).
-      const bool use_r16s = !(getenv("EMI_FFT_R16S") && atoi(getenv("EMI_FFT_R16S")) == 0);
-      if (!pl.r16 && need > 4096 && pl.sz % 2 == 0 && use_r16s) {
-        static const int r1ss[] = {
-#define EMI_R16S_ROW(r_) r_,
-            EMI_R16S_LIST(EMI_R16S_ROW)
-#undef EMI_R16S_ROW
-        };
-        for (int r : r1ss)
-          if (!pl.r16 && 256 * r >= pl.sz - 1) pl.r16 = r, pl.split = 2;
-      }
-      if (pl.r16) pl.blue = 1;
-    }
-    if (pl.r16) {
-      pl.S = 256 * pl.r16;
-      fac.assign(1, pl.r16);  // bookkeeping only: the factor list of these kernels is R1, 16, 16 at compile time
-    } else if (pl.blue) {
-      pl.S = emi::next_235(2 * pl.sz - 1);
-      emi::factorize_smooth(pl.S, fac);
-      // Specialised kernels (EMI_HOT_PLAN_LIST): the work length and factor list of the cheapest one that is long
-      // enough -- cost model S x (passes + 1), as next_235 -- replace the generic choice when they cost no more: that
-      // covers the merged tails (8, 8, 8, 6 | 9 | 10: one LDS round trip fewer than 8, 8, 8, 2, 3 ...) and any work length of the
-      // list that is not of the form 2^a {1,3,5,9,15} (there are none at present, see emi_types.h).
-      // Even NLOEN only: odd rows run the generic kernels, which have no composite butterflies.  The plan must be the
-      // one for the fields-per-workgroup this work length gets (the 40-KiB rule further down).
-      if (!pl.cmode && !getenv("EMI_FFT_NO_HOT")) {
-        static const int hp[][9] = {
-#define EMI_HOT_ROW(pc_, S_, nf_, a_, b_, c_, d_, e_, nfl_) {pc_, S_, nf_, a_, b_, c_, d_, e_, nfl_},
-            EMI_HOT_PLAN_LIST(EMI_HOT_ROW)
-#undef EMI_HOT_ROW
-        };
-        long long best = (long long)pl.S * (long long)(fac.size() + 1);
-        const int *pick = nullptr;
-        for (const auto &r : hp) {
-          if (r[1] < 2 * pl.sz - 1) continue;
-          int fbk_r = 16;
-          while (fbk_r > 1 && (size_t)fbk_r * FFT_LDS_ELEMS(r[1]) * 2 * P.esz > 40960) fbk_r >>= 1;
-          if (fbk_r < r[8]) continue;  // (the fp32 library has room for twice the fields: it runs the plan with the list's count, below)
-          const long long cost = (long long)r[1] * (r[2] + 1);
-          if (cost <= best) {  // list order: a merged tail (ids 22-27) comes after the plain list of its length
-            best = cost;
-            pick = r;
-          }
-        }
-        if (pick) {
-          pl.S = pick[1];
-          fac.assign(pick + 3, pick + 3 + pick[2]);
-        }
-      }
-    }
-    if (pl.S > 65535 || fac.size() > 14) EMI_FAIL(EMI_ERR_UNSUPPORTED, "FFT length %d not supported (work size %d)", n, pl.S);
-    pl.nfac = (int)fac.size();
-    for (int i = 0; i < pl.nfac; i++) pl.fac[i] = fac[i];
-    const int skey = pl.S * 16 + (pl.r16 ? 15 : (pl.mr ? 14 : pl.nfac));  // the tables depend on the factor list: merged and plain lists differ in length
-    auto si = sidx.find(skey);
-    if (si == sidx.end()) {
-      Shared sh{};
-      sh.S = pl.S;
-      sh.fac = fac;
-      sh.r16 = pl.r16;
-      sh.mr = pl.mr;
-      sh.tw_off = (int)n_tw;
-      sh.perm_off = (int)n_perm;
-      if (pl.mr) {
-        // twiddle bases of pass 2, [k1]: w^(C k1), and of pass 3, [k1 + A k2]: w^(k1 + A k2) (input r of a butterfly times base^r);
-        // perm[k] = LDS position of coefficient k
-        const int A = fac[0], B = fac[1];
-        sh.ptw_off[0] = (int)n_ptw;
-        n_ptw += (size_t)A;
-        sh.ptw_off[1] = (int)n_ptw;
-        n_ptw += (size_t)A * B;
-        sh.ptw_off[2] = (int)n_ptw;
-        n_perm += pl.S;
-      } else if (pl.r16) {
-        // the digit twiddles of A1 / B1: rows 0..2 = w^(t qa), qa = 1..3; rows 3..6 = w^(4 t qb), qb = 1..4; w = exp(-2 pi i / S), t < 256
-        sh.ptw_off[0] = (int)n_ptw;
-        n_ptw += 7 * 256;
-      } else {
-      n_tw += pl.S;
-      n_perm += pl.S;
-      long long lenp = 1;
-      for (int ip = 0; ip < pl.nfac; ip++) {
-        sh.ptw_off[ip] = (int)n_ptw;
-        if (lenp > 1) n_ptw += (size_t)(fac[ip] - 1) * lenp;
-        lenp *= fac[ip];
-      }
-      }
-      si = sidx.emplace(skey, (int)shared.size()).first;
-      shared.push_back(sh);
-    }
-    const Shared &sh = shared[si->second];
+    FftChoice c;
+    if (int rc = fft_choose(n, P.esz, sw, c)) return rc;
+    FftPlanDev &pl = c.pl;
+    const FftShared &sh = fft_share_tables(pl, sidx, shared, nt);
     pl.tw_off = sh.tw_off;
     pl.perm_off = sh.perm_off;
     for (int ip = 0; ip < pl.nfac; ip++) pl.ptw_off[ip] = sh.ptw_off[ip];
-    pl.rtw_off = (int)n_rtw;
-    n_rtw += pl.sz + 1;
+    pl.rtw_off = (int)nt.rtw;
+    nt.rtw += pl.sz + 1;
     if (pl.blue) {
-      pl.chirp_off = (int)n_chirp;
-      n_chirp += pl.split ? pl.sz / 2 : pl.sz;
-      pl.bhat_off = (int)n_bhat;
-      n_bhat += pl.S;
+      pl.chirp_off = (int)nt.chirp;
+      nt.chirp += pl.split ? pl.sz / 2 : pl.sz;
+      pl.bhat_off = (int)nt.bhat;
+      nt.bhat += pl.S;
     }
-    if (n_tw > 0x7fffffffULL || n_ptw > 0x7fffffffULL || n_bhat > 0x7fffffffULL) EMI_FAIL(EMI_ERR_UNSUPPORTED, "FFT tables too large");
-    // fields per workgroup: as many as fit ~40 KiB of LDS (power of two, <= 16); longer rows get one
-    // field per workgroup and more threads.  Threads per workgroup follow the LDS footprint: 256 up to
-    // 40 KiB, 512 up to 80 KiB, else 1024 -- i.e. always 16 waves per CU at 128 VGPRs.  (One thread per
-    // radix-8 butterfly, S/8, removes the idle lanes of the second sweep at S = 2560/3072/4608/5120
-    // but makes workgroups of 5, 9 and 10 waves, of which only one fits the 16-wave budget: measured
-    // 25 % slower.)
-    size_t per_field = (size_t)FFT_LDS_ELEMS(pl.S) * 2 * P.esz;
-    int fbk = 16;
-    while (fbk > 1 && fbk * per_field > 40960) fbk >>= 1;
-    pl.fbk = fbk;
-    size_t need = fbk * per_field;
-    // a row whose work array exceeds the 160 KiB of LDS (fp64: more than 10240 complex points -- the four longest rows of
-    // TCo2559, or any caller grid: the reference takes any KLOEN, ftdir_mod.F90:67-84) runs the same passes on a slice
-    // of a global scratch buffer (k_fft_*_gm): slow per row, but such rows are few
-    const bool gmem = need > 160 * 1024;
-    int nthr = need <= 40960 ? 256 : (need <= 81920 ? 512 : 1024);
-    // specialised kernel for this work length?  (Bluestein, even NLOEN, one field per workgroup)
-    int hot = 0;
-    if (pl.blue && !pl.cmode && !gmem && !getenv("EMI_FFT_NO_HOT")) {
-      static const int hp[][9] = {
-#define EMI_HOT_ROW(pc_, S_, nf_, a_, b_, c_, d_, e_, nfl_) {pc_, S_, nf_, a_, b_, c_, d_, e_, nfl_},
-          EMI_HOT_PLAN_LIST(EMI_HOT_ROW)
-#undef EMI_HOT_ROW
-      };
-      // The list's fields-per-workgroup are those of the fp64 library.  The fp32 library could hold twice as many in its 40 KiB, for which no
-      // kernel is compiled: until round 6 its short rows (work lengths <= 1536) therefore fell through to the generic kernels -- 14.7 of the
-      // 117 ms of FFT per pair at TCo1279 (profiles/r6_pmc_fft_fp32.txt: k_fft_dir 8.35 + k_fft_inv 6.32 ms).  They take the list's plan with
-      // the list's field count now (half the LDS per workgroup; the wave budget of the CU is what limits both).
-      int hot_fbk = 0;
-      for (const auto &r : hp) {
-        bool same = r[1] == pl.S && r[2] == pl.nfac && r[8] <= fbk;
-        for (int i = 0; same && i < pl.nfac; i++) same = r[3 + i] == pl.fac[i];
-        if (same) hot = r[0], hot_fbk = r[8];
-      }
-      if (hot) {
-        fbk = hot_fbk;
-        pl.fbk = fbk;
-        need = fbk * per_field;
-        nthr = need <= 40960 ? 256 : (need <= 81920 ? 512 : 1024);  // = hot_threads(pc): what the specialised kernels are compiled for
-      }
-    }
-    if (pl.r16) {  // one field per workgroup, 256 or 320 threads, one plane + the 240 small twiddles of LDS
-      hot = 0;
-      fbk = 1;
-      pl.fbk = 1;
-      nthr = 16 * pl.r16 > 256 ? roundup(16 * pl.r16, 64) : 256;
-    }
-    if (pl.mr) {
-      hot = 0;
-      fbk = mr_fbk;
-      pl.fbk = fbk;
-      nthr = mr_nthr;
-    }
-    for (int i = 0; i < pl.nfac; i++)
-      if (!hot && !pl.r16 && !pl.mr && (pl.fac[i] == 6 || pl.fac[i] > 8)) EMI_FAIL(EMI_ERR_RUNTIME, "internal: composite FFT radix %d without a specialised kernel (length %d)", pl.fac[i], n);
+    if (nt.tw > 0x7fffffffULL || nt.ptw > 0x7fffffffULL || nt.bhat > 0x7fffffffULL) EMI_FAIL(EMI_ERR_UNSUPPORTED, "FFT tables too large");
     int cls = -1;
-    for (size_t c = 0; c < P.fclass.size(); c++)
-      if (P.fclass[c].nthr == nthr && P.fclass[c].fbk == fbk && P.fclass[c].hot == hot && P.fclass[c].r16 == pl.r16 && P.fclass[c].split == pl.split && P.fclass[c].mr == pl.mr && P.fclass[c].gmem == (gmem && !pl.mr ? 1 : 0)) cls = (int)c;
+    for (size_t k = 0; k < P.fclass.size(); k++) {
+      const FftClass &fc = P.fclass[k];
+      if (fc.nthr == c.nthr && fc.fbk == pl.fbk && fc.hot == c.hot && fc.r16 == pl.r16 && fc.split == pl.split && fc.mr == pl.mr && fc.gmem == (int)c.gmem) cls = (int)k;
+    }
     if (cls < 0) {
       cls = (int)P.fclass.size();
       P.fclass.emplace_back();
-      P.fclass[cls].nthr = nthr;
-      P.fclass[cls].fbk = fbk;
-      P.fclass[cls].hot = hot;
-      P.fclass[cls].r16 = pl.r16;
-      P.fclass[cls].split = pl.split;
-      P.fclass[cls].mr = pl.mr;
-      P.fclass[cls].gmem = gmem && !pl.mr ? 1 : 0;
+      FftClass &fc = P.fclass[cls];
+      fc.nthr = c.nthr, fc.fbk = pl.fbk, fc.hot = c.hot, fc.r16 = pl.r16, fc.split = pl.split, fc.mr = pl.mr, fc.gmem = c.gmem;
     }
     pl.lds_class = cls;
-    int id = (int)P.fplans.size();
+    idx[n] = P.planid[j] = (int)P.fplans.size();
     P.fplans.push_back(pl);
-    idx[n] = id;
-    P.planid[j] = id;
   }
   // ---- pass 2: fill the tables
-  std::vector<d2> tw(n_tw), rtw(n_rtw), chirp(n_chirp), bhat(n_bhat), ptw(n_ptw);
-  std::vector<uint16_t> perm(n_perm);
-  emi::parallel_for((int)shared.size(), [&](int is) {
-    const Shared &sh = shared[is];
-    const int S = sh.S;
-    if (sh.mr) {
-      const int A = sh.fac[0], B = sh.fac[1], C = sh.fac[2], P1 = (B * C) | 1;
-      auto w = [&](long long e) {
-        long double a = 2.0L * (long double)M_PIl * (long double)(e % S) / (long double)S;
-        return d2{(double)cosl(a), (double)-sinl(a)};
-      };
-      d2 *t1 = ptw.data() + sh.ptw_off[0], *t2 = ptw.data() + sh.ptw_off[1];
-      for (int k1 = 0; k1 < A; k1++) t1[k1] = w((long long)C * k1);
-      for (int q = 0; q < A * B; q++) t2[q] = w((long long)q);
-      for (int k = 0; k < S; k++) perm[sh.perm_off + k] = (uint16_t)((k % A) * P1 + ((k / A) % B) * C + k / (A * B));
-      return;
-    }
-    if (sh.r16) {
-      d2 *dst = ptw.data() + sh.ptw_off[0];
-      for (int row = 0; row < 7; row++) {
-        const int mult = row < 3 ? row + 1 : 4 * (row - 2);
-        for (int t = 0; t < 256; t++) {
-          long double a = 2.0L * (long double)M_PIl * (long double)(((long long)t * mult) % S) / (long double)S;
-          *dst++ = d2{(double)cosl(a), (double)-sinl(a)};
-        }
-      }
-      return;
-    }
-    for (int k = 0; k < S; k++) {
-      long double a = 2.0L * (long double)M_PIl * (long double)k / (long double)S;
-      tw[sh.tw_off + k] = d2{(double)cosl(a), (double)-sinl(a)};
-    }
-    // per-pass twiddle tables, [t-1][j] with j fastest (coalesced reads)
-    long long lenp = 1;
-    for (size_t ip = 0; ip < sh.fac.size(); ip++) {
-      const int R = sh.fac[ip];
-      d2 *dst = ptw.data() + sh.ptw_off[ip];
-      if (lenp > 1)
-        for (int t = 1; t < R; t++)
-          for (long long j = 0; j < lenp; j++) {
-            long double a = 2.0L * (long double)M_PIl * (long double)((j * t) % (lenp * R)) / (long double)(lenp * R);
-            *dst++ = d2{(double)cosl(a), (double)-sinl(a)};
-          }
-      lenp *= R;
-    }
-    std::vector<uint16_t> pm;
-    emi::dit_positions(S, sh.fac, pm);
-    std::copy(pm.begin(), pm.end(), perm.begin() + sh.perm_off);
-  });
+  std::vector<d2> tw(nt.tw), rtw(nt.rtw), chirp(nt.chirp), bhat(nt.bhat), ptw(nt.ptw);
+  std::vector<uint16_t> perm(nt.perm);
+  emi::parallel_for((int)shared.size(), [&](int is) { fft_fill_shared(shared[is], tw, ptw, perm); });
   // longest rows first: their O(L * sz) filter sums dominate
   std::vector<int> order(P.fplans.size());
   for (size_t i = 0; i < order.size(); i++) order[i] = (int)i;
   std::sort(order.begin(), order.end(), [&](int a, int b) { return P.fplans[a].n > P.fplans[b].n; });
-  emi::parallel_for((int)order.size(), [&](int io) {
-    const FftPlanDev &pl = P.fplans[order[io]];
-    const int n = pl.n;
-    const double tpi = 2.0 * M_PI;
-    for (int k = 0; k <= pl.sz; k++) {
-      double a = tpi * (double)k / (double)n;
-      rtw[pl.rtw_off + k] = d2{std::cos(a), -std::sin(a)};
-    }
-    if (!pl.blue) return;
-    d2 *c = chirp.data() + pl.chirp_off;
-    const int csz = pl.split ? pl.sz / 2 : pl.sz;  // length of the chirp-z transform(s) of the row: the split kernels run two of sz / 2
-    for (int k = 0; k < csz; k++) {
-      long long k2 = ((long long)k * k) % (2LL * csz);
-      double a = M_PI * (double)k2 / (double)csz;
-      c[k] = d2{std::cos(a), -std::sin(a)};  // exp(-i pi k^2/csz)
-    }
-    // filter b_j = conj(c_|j|) wrapped to length L; Bhat = DFT_L(b) (direct O(L*sz) sum in
-    // long double: setup only, keeps the table accurate to ~1e-17), stored at the DIT positions
-    const int L = pl.S, r0 = pl.fac[0];
-    const uint16_t *pm = pl.r16 ? nullptr : perm.data() + pl.perm_off;
-    std::vector<long double> cr(L);
-    for (int k = 0; k < L; k++) cr[k] = cosl(2.0L * (long double)M_PIl * (long double)k / (long double)L);
-    d2 *bh = bhat.data() + pl.bhat_off;
-    for (int k = 0; k < L; k++) {
-      long double sr = c[0].x, si = -c[0].y;
-      long long jk = 0;
-      for (int jj = 1; jj < csz; jj++) {
-        // b_j + b_{L-j} term: conj(c_j) * (w^{jk} + w^{-jk}) = conj(c_j) * 2 cos(2 pi j k/L)
-        jk += k;
-        if (jk >= L) jk -= L;
-        long double cs = 2.0L * cr[jk];
-        sr += (long double)c[jj].x * cs;
-        si += -(long double)c[jj].y * cs;
-      }
-      // position p = pm[k] of the DIT-ordered spectrum belongs to the middle butterfly q = p / R0 as its
-      // element t = p % R0; stored [t][q] so that a wave reads its filter values coalesced
-      if (pl.r16) {
-        // k = k0 + R1 (k1 + 16 k2) sits in register k2 of thread 16 k0 + k1 of the fused middle pass: table [k2][16 k0 + k1]
-        const int k0 = k % pl.r16, kk = k / pl.r16, k1 = kk % 16, k2 = kk / 16;
-        bh[(size_t)k2 * (16 * pl.r16) + 16 * k0 + k1] = d2{(double)(sr / (long double)L), (double)(si / (long double)L)};  // the 1/S of the convolution folded in
-        continue;
-      }
-      const int p = pm[k];
-      bh[(size_t)(p % r0) * (L / r0) + p / r0] = d2{(double)sr, (double)si};
-    }
-  });
+  emi::parallel_for((int)order.size(), [&](int io) { fft_fill_length(P.fplans[order[io]], perm, rtw, chirp, bhat); });
   for (int j = 0; j < P.nlat; j++) {
     const FftPlanDev &pl = P.fplans[P.planid[j]];
     FftClass &fc = P.fclass[pl.lds_class];
@@ -862,34 +910,19 @@ static int build_fft_plans(Plan &P) {
       long double a = 2.0L * (long double)M_PIl * (long double)(c * k1) / 256.0L;
       tw256[(k1 - 1) * 16 + c] = d2{(double)cosl(a), (double)-sinl(a)};
     }
-  void *d_tw, *d_rtw, *d_chirp, *d_bhat, *d_ptw, *d_tw256;
-  uint16_t *d_perm;
-  FftPlanDev *d_plans;
-  int *d_planid;
   // the tables are computed in (long) double and rounded once for the fp32 library
-  auto upload_c = [&](const std::vector<d2> &v, void **d) {
-    if (P.esz == 8) return upload(v, (d2 **)d);
+  auto upload_c = [&](const std::vector<d2> &v, const void **d) {
+    if (P.esz == 8) return upload(P.dev_allocs, v, d);
     std::vector<f2> w(v.size());
     for (size_t i = 0; i < v.size(); i++) w[i] = f2{(float)v[i].x, (float)v[i].y};
-    return upload(w, (f2 **)d);
+    return upload(P.dev_allocs, w, d);
   };
-  if (upload_c(tw, &d_tw) || upload_c(ptw, &d_ptw) || upload_c(rtw, &d_rtw) || upload_c(chirp, &d_chirp) || upload_c(bhat, &d_bhat) || upload_c(tw256, &d_tw256) || upload(perm, &d_perm) ||
-      upload(P.fplans, &d_plans) || upload(P.planid, &d_planid))
+  FftTabDev &ft = P.ftab;
+  if (upload_c(tw, &ft.tw) || upload_c(ptw, &ft.ptw) || upload_c(rtw, &ft.rtw) || upload_c(chirp, &ft.chirp) || upload_c(bhat, &ft.bhat) || upload_c(tw256, &ft.tw256) ||
+      upload(P.dev_allocs, perm, &ft.perm) || upload(P.dev_allocs, P.fplans, &ft.plans) || upload(P.dev_allocs, P.planid, &ft.planid))
     return EMI_ERR_RUNTIME;
-  for (void *p : {d_tw, d_ptw, d_rtw, d_chirp, d_bhat, d_tw256, (void *)d_perm, (void *)d_plans, (void *)d_planid})
-    P.dev_allocs.push_back(p);
-  P.ftab.tw = d_tw;
-  P.ftab.ptw = d_ptw;
-  P.ftab.rtw = d_rtw;
-  P.ftab.chirp = d_chirp;
-  P.ftab.bhat = d_bhat;
-  P.ftab.tw256 = d_tw256;
-  P.ftab.perm = d_perm;
-  P.ftab.plans = d_plans;
-  P.ftab.planid = d_planid;
   for (FftClass &fc : P.fclass) {
-    if (upload(fc.lats, &fc.d_lats)) return EMI_ERR_RUNTIME;
-    P.dev_allocs.push_back(fc.d_lats);
+    if (upload(P.dev_allocs, fc.lats, &fc.d_lats)) return EMI_ERR_RUNTIME;
     std::vector<FftRowDev> rows(fc.lats.size());
     for (size_t i = 0; i < fc.lats.size(); i++) {
       const int j = fc.lats[i];
@@ -901,8 +934,7 @@ static int build_fft_plans(Plan &P) {
       r.mr_abc = pl.mr ? (pl.fac[0] | (pl.fac[1] << 8) | (pl.fac[2] << 16) | (pl.fbk << 24)) : 0;
       r.racthe = P.racthe[P.lat0 + j], r.rw = P.rw[P.lat0 + j];
     }
-    if (upload(rows, &fc.d_rows)) return EMI_ERR_RUNTIME;
-    P.dev_allocs.push_back(fc.d_rows);
+    if (upload(P.dev_allocs, rows, &fc.d_rows)) return EMI_ERR_RUNTIME;
   }
   return 0;
 }
@@ -988,8 +1020,27 @@ static int legpol_index(LegpolSource &src, int nsmax, int ndgnh, const std::vect
 
 static int legpol_write(int kresol, const char *fname);
 
-extern "C" int emi_setup_legpol(const emi_setup_t *cfg, const emi_legpol_io_t *io, int *kresol) {
-  EmiRange rg_setup(EMI_LBL_SETUP);  // GSTATS 2
+// ---- SETUP_TRANS in stages.  emi_setup_legpol (the driver, at the end) calls them in this order; each takes what it reads and fills as its
+// arguments.  What describes the plan lives in Plan; SetupTables carries the host images of the device tables the plan does not keep.
+enum LegpolMode { LP_NONE, LP_READF, LP_WRITEF, LP_MEMBUF };
+struct SetupTables {
+  std::vector<int> ebase, rowm;                      // local index tables
+  std::vector<double> eps, specw, lapin, l_rw, l_racthe;
+  std::vector<int> legN, legS, fftrow;               // Fourier-buffer row tables
+  bool rowtable = false;                             // several tasks (or EMI_TEST_PATHS bit 0): the FFT side looks its rows up in fftrow
+};
+struct SetupClock {  // EMI_SETUP_TIMING=1 prints where SETUP_TRANS spends its wall time
+  const bool on = getenv("EMI_SETUP_TIMING") && atoi(getenv("EMI_SETUP_TIMING"));
+  double t = now();
+  static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+  void phase(const char *what) {
+    if (on) fprintf(stderr, "[emi_setup] %-28s %8.3f s\n", what, now() - t);
+    t = now();
+  }
+};
+
+// stage 1: the arguments and the CDIO_LEGPOL mode (setup_trans.F90:360-384)
+static int setup_arguments(const emi_setup_t *cfg, const emi_legpol_io_t *io, LegpolMode *lp_mode) {
   if (!G.init) EMI_FAIL(EMI_ERR_STATE, "SETUP_TRANS: SETUP_TRANS0 HAS TO BE CALLED BEFORE SETUP_TRANS");
   if (!cfg) EMI_FAIL(EMI_ERR_ARG, "emi_setup: null config");
   if (cfg->kdgl <= 0 || cfg->kdgl % 2 != 0) EMI_FAIL(EMI_ERR_ARG, "SETUP_TRANS: KDGL IS NOT A POSITIVE, EVEN NUMBER");
@@ -999,59 +1050,34 @@ extern "C" int emi_setup_legpol(const emi_setup_t *cfg, const emi_legpol_io_t *i
   if (cfg->precision != 0 && cfg->precision != 8 && cfg->precision != 4)
     EMI_FAIL(EMI_ERR_ARG, "emi_setup: precision must be 8 (fp64, the _dp library) or 4 (fp32, _sp), got %d", cfg->precision);
   if (cfg->ksmax < 0) EMI_FAIL(EMI_ERR_ARG, "SETUP_TRANS: KSMAX < 0");
-  // CDIO_LEGPOL (setup_trans.F90:360-384)
-  enum { LP_NONE, LP_READF, LP_WRITEF, LP_MEMBUF } lp_mode = LP_NONE;
+  *lp_mode = LP_NONE;
   if (io && io->io && io->io[0]) {
     std::string mode(io->io);
     while (!mode.empty() && mode.back() == ' ') mode.pop_back();
     if (G.nproc_all > 1) EMI_FAIL(EMI_ERR_UNSUPPORTED, "SETUP_TRANS:CDIO_LEGPOL OPTIONS ONLY FOR NPROC=1 ");
     if (mode == "readf" || mode == "READF")
-      lp_mode = LP_READF;
+      *lp_mode = LP_READF;
     else if (mode == "writef" || mode == "WRITEF")
-      lp_mode = LP_WRITEF;
+      *lp_mode = LP_WRITEF;
     else if (mode == "membuf" || mode == "MEMBUF")
-      lp_mode = LP_MEMBUF;
+      *lp_mode = LP_MEMBUF;
     else
       EMI_FAIL(EMI_ERR_ARG, "SETUP_TRANS:CDIO_LEGPOL UNKNOWN METHOD (%s)", mode.c_str());
-    if (lp_mode != LP_MEMBUF && (!io->fname || !io->fname[0])) EMI_FAIL(EMI_ERR_ARG, "SETUP_TRANS: CDLEGPOLFNAME ARGUMENT MISSING");
+    if (*lp_mode != LP_MEMBUF && (!io->fname || !io->fname[0])) EMI_FAIL(EMI_ERR_ARG, "SETUP_TRANS: CDLEGPOLFNAME ARGUMENT MISSING");
   }
-  LegpolSource lp_src;
-  if ((lp_mode == LP_READF || lp_mode == LP_MEMBUF) && legpol_open(lp_src, io, lp_mode == LP_MEMBUF)) return EMI_ERR_ARG;
-  const bool lp_read = lp_src.base != nullptr;
-  int slot = -1;
-  for (int i = 0; i < G.max_resol; i++)
-    if (!G.plans[i] || !G.plans[i]->active) {
-      slot = i;
-      break;
-    }
-  if (slot < 0) EMI_FAIL(EMI_ERR_STATE, "SETUP_TRANS:IDEF_RESOL > NMAX_RESOL");
-  Plan *pp = new Plan();
-  Plan &P = *pp;
-  P.nsmax = cfg->ksmax;
-  P.ndgl = cfg->kdgl;
-  P.ndgnh = (P.ndgl + 1) / 2;
-  P.ra = G.ra;
-  P.esz = cfg->precision == 4 ? 4 : 8;
-  P.nproc = G.nproc;
-  P.me = G.myproc - 1;
-  const int N = P.nsmax, L = P.ndgl, NP = P.nproc, me = P.me;
-  if (G.nproc_all > 1 && !G.a2a) {
-    delete pp;
-    EMI_FAIL(EMI_ERR_STATE, "SETUP_TRANS: %d tasks but no all-to-all-v hook registered (emi_set_alltoallv)", G.nproc_all);
-  }
-  if (NP > L / 2 || NP > N + 1) {
-    delete pp;
-    EMI_FAIL(EMI_ERR_ARG, "SETUP_TRANS: too many tasks (%d) for NDGL=%d, NSMAX=%d", NP, L, N);
-  }
+  return 0;
+}
+
+// stage 2: the global geometry of P.nsmax / P.ndgl -- NLOEN and the point offsets cum[0 .. NDGL], the Gaussian latitudes and weights,
+// cos^2 and 1 / (a cos) (suleg_mod.F90:264-293, 386-394), the wavenumber cut-offs NMEN / NDGLU
+static int setup_geometry(const emi_setup_t *cfg, Plan &P, std::vector<long long> &cum) {
+  const int L = P.ndgl;
   int ndlon = cfg->kdlon > 0 ? cfg->kdlon : 2 * L;
   P.nloen.assign(L, ndlon);
   if (cfg->kloen) {
     ndlon = 0;
     for (int j = 0; j < L; j++) {
-      if (cfg->kloen[j] <= 0) {
-        delete pp;
-        EMI_FAIL(EMI_ERR_ARG, "SETUP_TRANS: KLOEN INVALID (ONE or MORE POINTS <= 0)");
-      }
+      if (cfg->kloen[j] <= 0) EMI_FAIL(EMI_ERR_ARG, "SETUP_TRANS: KLOEN INVALID (ONE or MORE POINTS <= 0)");
       ndlon = std::max(ndlon, cfg->kloen[j]);
     }
     for (int j = 0; j < L; j++) {
@@ -1059,25 +1085,12 @@ extern "C" int emi_setup_legpol(const emi_setup_t *cfg, const emi_legpol_io_t *i
       if (cfg->kloen[j] != ndlon) P.reduced = true;
     }
   }
-  P.nspec2g = (N + 1) * (N + 2);
-  std::vector<long long> cum(L + 1, 0);
+  P.nspec2g = (P.nsmax + 1) * (P.nsmax + 2);
+  cum.assign(L + 1, 0);
   for (int j = 0; j < L; j++) cum[j + 1] = cum[j] + P.nloen[j];
-  if (cum[L] > 2000000000LL) {
-    delete pp;
-    EMI_FAIL(EMI_ERR_UNSUPPORTED, "grid too large for 32-bit point offsets");
-  }
+  if (cum[L] > 2000000000LL) EMI_FAIL(EMI_ERR_UNSUPPORTED, "grid too large for 32-bit point offsets");
   P.ngptotg = (int)cum[L];
-  // Gaussian latitudes / weights, cos^2, 1/(a cos)  (suleg_mod.F90:264-293, 386-394)
-  // EMI_SETUP_TIMING=1 prints where SETUP_TRANS spends its wall time
-  const bool timing = getenv("EMI_SETUP_TIMING") && atoi(getenv("EMI_SETUP_TIMING"));
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double t_ph = now();
-  auto phase = [&](const char *what) {
-    if (timing) fprintf(stderr, "[emi_setup] %-28s %8.3f s\n", what, now() - t_ph);
-    t_ph = now();
-  };
   emi::gauss_latitudes(L, P.rmu, P.rw);
-  phase("gaussian latitudes");
   P.cos2.assign(L, 0.0);
   P.racthe.assign(L, 0.0);
   for (int j = 0; j < L; j++) {
@@ -1085,28 +1098,27 @@ extern "C" int emi_setup_legpol(const emi_setup_t *cfg, const emi_legpol_io_t *i
     P.cos2[j] = c * c;
     P.racthe[j] = 1.0 / c / P.ra;
   }
-  emi::wavenumber_cutoffs(N, L, P.nloen, P.reduced, P.cos2, P.nmen, P.ndglu);
-  if (lp_read && legpol_index(lp_src, N, P.ndgnh, P.nloen, P.nmen, P.ndglu)) {
-    delete pp;
-    return EMI_ERR_ARG;
-  }
+  emi::wavenumber_cutoffs(P.nsmax, L, P.nloen, P.reduced, P.cos2, P.nmen, P.ndglu);
+  return 0;
+}
 
-  // ---- distribution over tasks
+// stage 3: the distribution over NPRTRW x NPRTRV tasks, identical on every task: the W-set of every wavenumber, the latitude
+// band of every W-set and its cut into the grid shares of the V-sets
+static int setup_distribution(int N, int L, const std::vector<int> &nloen, const std::vector<long long> &cum, int nprw, int nprv,
+                              std::vector<int> &procm, std::vector<int> &latlo, std::vector<int> &vlat) {
   // wavenumbers: the reference's zig-zag W-set assignment (suwavedi_mod.F90:118-137)
-  P.procm.assign(N + 1, 0);
-  {
-    int ik = 0, ind = 1;
-    for (int m = 0; m <= N; m++) {
-      ik += ind;
-      if (ik > NP) {
-        ik = NP;
-        ind = -1;
-      } else if (ik < 1) {
-        ik = 1;
-        ind = 1;
-      }
-      P.procm[m] = ik - 1;
+  procm.assign(N + 1, 0);
+  int ik = 0, ind = 1;
+  for (int m = 0; m <= N; m++) {
+    ik += ind;
+    if (ik > nprw) {
+      ik = nprw;
+      ind = -1;
+    } else if (ik < 1) {
+      ik = 1;
+      ind = 1;
     }
+    procm[m] = ik - 1;
   }
   // latitudes: contiguous bands of whole latitudes (the Fourier-space distribution of sumplatb_mod.F90 with
   // LDSPLIT=.FALSE., which weighs a latitude by NLOEN); the grid-point distribution is chosen identical, so
@@ -1117,139 +1129,131 @@ extern "C" int emi_setup_legpol(const emi_setup_t *cfg, const emi_legpol_io_t *i
   // job's pace (the reference's weight is NLOEN).
   std::vector<long long> wcum(L + 1, 0);
   for (int j = 0; j < L; j++) {
-    const double n = (double)P.nloen[j];
+    const double n = (double)nloen[j];
     const double w = n * (n <= 1500.0 ? 20.0 : std::max(15.0, 20.0 - (n - 1500.0) * 0.00091)) + 1750.0;
     wcum[j + 1] = wcum[j] + (long long)(w + 0.5);
   }
-  P.latlo.assign(NP + 1, 0);
-  for (int r = 1; r < NP; r++) {
-    long long target = wcum[L] * r / NP;
+  latlo.assign(nprw + 1, 0);
+  for (int r = 1; r < nprw; r++) {
+    long long target = wcum[L] * r / nprw;
     int j = (int)(std::lower_bound(wcum.begin(), wcum.end(), target) - wcum.begin());
-    j = std::max(j, P.latlo[r - 1] + 1);
-    j = std::min(j, L - (NP - r));
-    P.latlo[r] = j;
+    j = std::max(j, latlo[r - 1] + 1);
+    j = std::min(j, L - (nprw - r));
+    latlo[r] = j;
   }
-  P.latlo[NP] = L;
+  latlo[nprw] = L;
   // V-sets: every band in NPRTRV sub-bands of whole latitudes with (nearly) equal numbers of points -- the grid-point
   // distribution over all NPROC tasks (the reference: sumplat with NPRGPNS = NPROC bands; whole latitudes here as for the bands)
-  P.nprv = G.nprtrv;
-  P.mev = G.mysetv - 1;
-  if (P.nprv > 1) {
-    P.vlat.assign((size_t)NP * P.nprv + 1, L);
-    for (int w = 0; w < NP; w++) {
-      const int a0 = P.latlo[w], a1 = P.latlo[w + 1];
-      if (a1 - a0 < P.nprv) {
-        delete pp;
-        EMI_FAIL(EMI_ERR_ARG, "SETUP_TRANS: too many tasks: band %d has %d latitudes for %d V-sets", w + 1, a1 - a0, P.nprv);
-      }
-      P.vlat[(size_t)w * P.nprv] = a0;
-      for (int v = 1; v < P.nprv; v++) {
-        const long long target = cum[a0] + (cum[a1] - cum[a0]) * v / P.nprv;
+  if (nprv > 1) {
+    vlat.assign((size_t)nprw * nprv + 1, L);
+    for (int w = 0; w < nprw; w++) {
+      const int a0 = latlo[w], a1 = latlo[w + 1];
+      if (a1 - a0 < nprv) EMI_FAIL(EMI_ERR_ARG, "SETUP_TRANS: too many tasks: band %d has %d latitudes for %d V-sets", w + 1, a1 - a0, nprv);
+      vlat[(size_t)w * nprv] = a0;
+      for (int v = 1; v < nprv; v++) {
+        const long long target = cum[a0] + (cum[a1] - cum[a0]) * v / nprv;
         int j = (int)(std::lower_bound(cum.begin() + a0, cum.begin() + a1, target) - cum.begin());
-        j = std::max(j, P.vlat[(size_t)w * P.nprv + v - 1] + 1);
-        j = std::min(j, a1 - (P.nprv - v));
-        P.vlat[(size_t)w * P.nprv + v] = j;
+        j = std::max(j, vlat[(size_t)w * nprv + v - 1] + 1);
+        j = std::min(j, a1 - (nprv - v));
+        vlat[(size_t)w * nprv + v] = j;
       }
     }
   }
-  P.lat0 = P.latlo[me];
-  P.nlat = P.latlo[me + 1] - P.lat0;
-  P.ngptot = (int)(cum[P.latlo[me + 1]] - cum[P.lat0]);
+  return 0;
+}
+
+// stage 4: this task's share (W-set P.me of the distribution) and its local index tables
+static void setup_local_tables(Plan &P, const std::vector<long long> &cum, SetupTables &T) {
+  const int N = P.nsmax;
+  P.lat0 = P.latlo[P.me];
+  P.nlat = P.latlo[P.me + 1] - P.lat0;
+  P.ngptot = (int)(cum[P.latlo[P.me + 1]] - cum[P.lat0]);
   for (int m = 0; m <= N; m++)
-    if (P.procm[m] == me) P.mval.push_back(m);
+    if (P.procm[m] == P.me) P.mval.push_back(m);
   P.nump = (int)P.mval.size();
   const int NU = P.nump, NL = P.nlat;
-  auto band_of = [&](int lat) { return (int)(std::upper_bound(P.latlo.begin(), P.latlo.end(), lat) - P.latlo.begin()) - 1; };
-
-  // ---- local index tables
-  P.nasm0.assign(NU, 0);
-  P.wbase.assign(NU + 1, 0);
-  P.wrows.assign(NU, 0);
-  P.ldp.assign(NU, 0);
-  P.ldk.assign(NU, 0);
-  P.offS.assign(NU, 0);
-  P.offA.assign(NU, 0);
-  P.offTS.assign(NU, 0);
-  P.offTA.assign(NU, 0);
-  P.lattile_pref.assign(NU + 1, 0);
-  P.ktile_pref.assign(NU + 1, 0);
-  P.lbase.assign(NU + 1, 0);
-  std::vector<int> ebase(NU, 0);
-  std::vector<double> eps, specw;
-  {
-    int ipos = 0;
-    long long poff = 0, ptoff = 0;
-    for (int ml = 0; ml < NU; ml++) {
-      const int m = P.mval[ml];
-      P.nasm0[ml] = ipos;  // 0-based (D%NASM0 - 1, suwavedi_mod.F90:128-133)
-      ipos += (N - m + 1) * 2;
-      for (int n = m; n <= N; n++) {  // SPNORMD weights (spnormd_mod.F90:40-57)
-        specw.push_back(m == 0 ? 1.0 : 2.0);
-        specw.push_back(m == 0 ? 0.0 : 2.0);
-      }
-      P.wrows[ml] = roundup(N + 2 - m, P.esz == 4 ? 32 : 16);  // whole stages of k_leg_inv: 8 (fp64) | 16 (fp32) rows per parity (LG_KR)
-      P.wbase[ml + 1] = P.wbase[ml] + P.wrows[ml];
-      int nd = std::min(P.ndgnh, P.ndglu[m]);
-      P.lbase[ml + 1] = P.lbase[ml] + nd;
-      P.ldp[ml] = roundup(std::max(nd, 1), 64);
-      long long pan = (long long)(P.wrows[ml] / 2) * P.ldp[ml];
-      P.offS[ml] = poff;
-      P.offA[ml] = poff + pan;
-      poff += 2 * pan;
-      P.ldk[ml] = roundup(P.wrows[ml] / 2, 128);  // whole 128-k tiles of k_leg_dir (zero padded)
-      long long pant = (long long)roundup(std::max(nd, 1), 16) * P.ldk[ml];  // k_leg_dir reads stages of 16 latitudes in both precisions (LG_LS; the fp32 kernel's 32-latitude stages went in round 5)
-      P.offTS[ml] = ptoff;
-      P.offTA[ml] = ptoff + pant;
-      ptoff += 2 * pant;
-      P.lattile_pref[ml + 1] = P.lattile_pref[ml] + (nd + 63) / 64;
-      {  // k_leg_dir's row tiles.  fp64: 2 per 128 n-pairs (one parity each), and for the rest none | one two-parity tile (<= 64 n-pairs) | two;
-         // fp32: two-parity tiles of 64 n-pairs
-        const int nk = P.wrows[ml] / 2, r = nk % 128;
-        P.ktile_pref[ml + 1] = P.ktile_pref[ml] + (P.esz == 4 ? (nk + 63) / 64 : 2 * (nk / 128) + (r == 0 ? 0 : r <= 64 ? 1 : 2));
-      }
-      ebase[ml] = (int)eps.size();
-      for (int n = m; n <= N + 2; n++)  // REPSNM (pre_suleg_mod.F90:55-63)
-        eps.push_back(std::sqrt((double)(n * n - m * m) / (double)(4 * n * n - 1)));
+  for (auto *v : {&P.nasm0, &P.wrows, &P.ldp, &P.ldk, &T.ebase}) v->assign(NU, 0);
+  for (auto *v : {&P.wbase, &P.lbase, &P.lattile_pref, &P.ktile_pref}) v->assign(NU + 1, 0);
+  for (auto *v : {&P.offS, &P.offA, &P.offTS, &P.offTA}) v->assign(NU, 0);
+  int ipos = 0;
+  long long poff = 0, ptoff = 0;
+  for (int ml = 0; ml < NU; ml++) {
+    const int m = P.mval[ml];
+    P.nasm0[ml] = ipos;  // 0-based (D%NASM0 - 1, suwavedi_mod.F90:128-133)
+    ipos += (N - m + 1) * 2;
+    for (int n = m; n <= N; n++) {  // SPNORMD weights (spnormd_mod.F90:40-57)
+      T.specw.push_back(m == 0 ? 1.0 : 2.0);
+      T.specw.push_back(m == 0 ? 0.0 : 2.0);
     }
-    P.nspec2 = ipos;
-    P.p_elems = poff;
-    P.pt_elems = ptoff;
-    P.wrows_total = P.wbase[NU];
+    P.wrows[ml] = roundup(N + 2 - m, P.esz == 4 ? 32 : 16);  // whole stages of k_leg_inv: 8 (fp64) | 16 (fp32) rows per parity (LG_KR)
+    P.wbase[ml + 1] = P.wbase[ml] + P.wrows[ml];
+    int nd = std::min(P.ndgnh, P.ndglu[m]);
+    P.lbase[ml + 1] = P.lbase[ml] + nd;
+    P.ldp[ml] = roundup(std::max(nd, 1), 64);
+    long long pan = (long long)(P.wrows[ml] / 2) * P.ldp[ml];
+    P.offS[ml] = poff;
+    P.offA[ml] = poff + pan;
+    poff += 2 * pan;
+    P.ldk[ml] = roundup(P.wrows[ml] / 2, 128);  // whole 128-k tiles of k_leg_dir (zero padded)
+    long long pant = (long long)roundup(std::max(nd, 1), 16) * P.ldk[ml];  // k_leg_dir reads stages of 16 latitudes in both precisions (LG_LS)
+    P.offTS[ml] = ptoff;
+    P.offTA[ml] = ptoff + pant;
+    ptoff += 2 * pant;
+    P.lattile_pref[ml + 1] = P.lattile_pref[ml] + (nd + 63) / 64;
+    {  // k_leg_dir's row tiles.  fp64: 2 per 128 n-pairs (one parity each), and for the rest none | one two-parity tile (<= 64 n-pairs) | two;
+       // fp32: two-parity tiles of 64 n-pairs
+      const int nk = P.wrows[ml] / 2, r = nk % 128;
+      P.ktile_pref[ml + 1] = P.ktile_pref[ml] + (P.esz == 4 ? (nk + 63) / 64 : 2 * (nk / 128) + (r == 0 ? 0 : r <= 64 ? 1 : 2));
+    }
+    T.ebase[ml] = (int)T.eps.size();
+    for (int n = m; n <= N + 2; n++)  // REPSNM (pre_suleg_mod.F90:55-63)
+      T.eps.push_back(std::sqrt((double)(n * n - m * m) / (double)(4 * n * n - 1)));
   }
-  std::vector<int> rowm(P.wrows_total);
+  P.nspec2 = ipos;
+  P.p_elems = poff;
+  P.pt_elems = ptoff;
+  P.wrows_total = P.wbase[NU];
+  T.rowm.resize(P.wrows_total);
   for (int ml = 0; ml < NU; ml++)
-    for (int r = 0; r < P.wrows[ml]; r++) rowm[P.wbase[ml] + r] = ml;
+    for (int r = 0; r < P.wrows[ml]; r++) T.rowm[P.wbase[ml] + r] = ml;
   P.l_nmen.assign(NL, 0);
   P.l_gpoff.assign(NL, 0);
   P.l_fbase.assign(NL + 1, 0);
-  std::vector<double> l_rw(NL), l_racthe(NL);
+  T.l_rw.resize(NL);
+  T.l_racthe.resize(NL);
   for (int jl = 0; jl < NL; jl++) {
     const int j = P.lat0 + jl;
     P.l_nmen[jl] = P.nmen[j];
     P.l_gpoff[jl] = (int)(cum[j] - cum[P.lat0]);
     P.l_fbase[jl + 1] = P.l_fbase[jl] + P.nmen[j] + 1;
-    l_rw[jl] = P.rw[j];
-    l_racthe[jl] = P.racthe[j];
+    T.l_rw[jl] = P.rw[j];
+    T.l_racthe[jl] = P.racthe[j];
   }
   P.frows = P.l_fbase[NL];
   P.lrows = 2LL * P.lbase[NU];
+  T.lapin.assign(N + 4, 0.0);  // RLAPIN(-1:N+2) (pre_suleg_mod.F90:64-69)
+  for (int n = 1; n <= N + 2; n++) T.lapin[n + 1] = -(P.ra * P.ra / (double)(n * (n + 1)));
+}
 
-  // ---- Fourier-buffer row tables.  One task: both sides share one latitude-major buffer
-  // (row = fbase[lat] + m).  Several tasks: the Legendre-side buffer is cut into one block per
-  // destination task, the FFT-side buffer into one block per source task with exactly the same row
-  // order, so the all-to-all-v moves whole blocks.  Inside a block the rows are latitude-major, then
-  // wavenumber -- the order of the one-task buffer restricted to the block: an FFT workgroup then finds the
-  // wavenumbers of its latitude in NPROC short contiguous runs.  (The other order, wavenumber-major, makes
-  // every Fourier row of a latitude a separate far-apart line: measured on one task, EMI_FB_ORDER=m with
-  // EMI_FB_TABLE=1, the FFT kernels are 13-20 % slower and the Legendre kernels 1 % faster; the row table
-  // itself costs the FFT kernels 1.5 %.)
-  std::vector<int> legN(std::max(P.lbase[NU], 1)), legS(std::max(P.lbase[NU], 1)), fftrow(P.frows);  // never empty: k_leg_dir clamps its look-ups to an entry that exists
-  P.leg_rows.assign(NP, 0);
-  P.leg_disp.assign(NP, 0);
-  P.fft_rows.assign(NP, 0);
-  P.fft_disp.assign(NP, 0);
-  const bool tables = NP > 1 || (test_paths() & 1);  // one task: plain affine rows, no table
-  if (!tables) {
+// stage 5: the Fourier-buffer row tables.  One task: both sides share one latitude-major buffer
+// (row = fbase[lat] + m).  Several tasks: the Legendre-side buffer is cut into one block per
+// destination task, the FFT-side buffer into one block per source task with exactly the same row
+// order, so the all-to-all-v moves whole blocks.  Inside a block the rows are latitude-major, then
+// wavenumber -- the order of the one-task buffer restricted to the block: an FFT workgroup then finds the
+// wavenumbers of its latitude in NPROC short contiguous runs.  (The other order, wavenumber-major, makes
+// every Fourier row of a latitude a separate far-apart line: measured on one task, EMI_FB_ORDER=m with
+// EMI_FB_TABLE=1, the FFT kernels are 13-20 % slower and the Legendre kernels 1 % faster; the row table
+// itself costs the FFT kernels 1.5 %.)
+// `exchange_order`: the tables of several tasks (also on one task: EMI_TEST_PATHS bit 0); else plain affine rows, no table on the FFT side.
+static int setup_row_tables(Plan &P, bool exchange_order, SetupTables &T) {
+  const int N = P.nsmax, L = P.ndgl, NP = P.nproc, NU = P.nump, NL = P.nlat;
+  std::vector<int> &legN = T.legN, &legS = T.legS, &fftrow = T.fftrow;
+  legN.assign(std::max(P.lbase[NU], 1), 0);  // never empty: k_leg_dir clamps its look-ups to an entry that exists
+  legS.assign(std::max(P.lbase[NU], 1), 0);
+  fftrow.assign(P.frows, 0);
+  T.rowtable = exchange_order;
+  for (auto *v : {&P.leg_rows, &P.leg_disp, &P.fft_rows, &P.fft_disp}) v->assign(NP, 0);
+  if (!exchange_order) {
     for (int ml = 0; ml < NU; ml++) {
       const int m = P.mval[ml], nd = P.lbase[ml + 1] - P.lbase[ml], isl0 = P.ndgnh - nd;
       for (int j = 0; j < nd; j++) {
@@ -1259,265 +1263,260 @@ extern "C" int emi_setup_legpol(const emi_setup_t *cfg, const emi_legpol_io_t *i
     }
     for (long long i = 0; i < P.frows; i++) fftrow[i] = (int)i;
     P.leg_rows[0] = P.fft_rows[0] = P.frows;
-  } else {
-    for (int ml = 0; ml < NU; ml++)
-      if (ml > 0 && P.mval[ml] <= P.mval[ml - 1]) {
-        delete pp;
-        EMI_FAIL(EMI_ERR_RUNTIME, "internal: local wavenumbers not ascending");
-      }
-    // Legendre side: block d holds the rows (lat in band d, local wavenumber ml with m <= NMEN(lat))
-    for (int ml = 0; ml < NU; ml++) {
-      const int m = P.mval[ml];
-      for (int lat = 0; lat < L; lat++)
-        if (P.nmen[lat] >= m) P.leg_rows[band_of(lat)]++;
-    }
-    for (int d = 1; d < NP; d++) P.leg_disp[d] = P.leg_disp[d - 1] + P.leg_rows[d - 1];
-    {
-      std::vector<long long> pos(P.leg_disp);
-      {
-        // the local wavenumbers are ascending, so those present at a latitude are ml = 0 .. cnt-1 and the
-        // row of (lat, ml) is the first row of the latitude + ml
-        std::vector<long long> latbase(L);
-        for (int lat = 0; lat < L; lat++) {
-          const int cnt = (int)(std::upper_bound(P.mval.begin(), P.mval.end(), P.nmen[lat]) - P.mval.begin());
-          latbase[lat] = pos[band_of(lat)];
-          pos[band_of(lat)] += cnt;
-        }
-        for (int ml = 0; ml < NU; ml++) {
-          const int nd = P.lbase[ml + 1] - P.lbase[ml], isl0 = P.ndgnh - nd;
-          for (int j = 0; j < nd; j++) {
-            legN[P.lbase[ml] + j] = (int)(latbase[isl0 + j] + ml);
-            legS[P.lbase[ml] + j] = (int)(latbase[L - 1 - isl0 - j] + ml);
-          }
-        }
-      }
-    }
-    // FFT side: block s holds the rows (local lat, wavenumber m of task s with m <= NMEN(lat)), same order
-    for (int m = 0; m <= N; m++)
-      for (int jl = 0; jl < NL; jl++)
-        if (P.l_nmen[jl] >= m) P.fft_rows[P.procm[m]]++;
-    for (int sr = 1; sr < NP; sr++) P.fft_disp[sr] = P.fft_disp[sr - 1] + P.fft_rows[sr - 1];
-    {
-      std::vector<long long> pos(P.fft_disp);
-      for (int jl = 0; jl < NL; jl++)
-        for (int m = 0; m <= P.l_nmen[jl]; m++) fftrow[P.l_fbase[jl] + m] = (int)pos[P.procm[m]]++;
-    }
-    long long tl = 0, tf = 0;
-    for (int r = 0; r < NP; r++) tl += P.leg_rows[r], tf += P.fft_rows[r];
-    if (tl != P.lrows || tf != P.frows) {
-      delete pp;
-      EMI_FAIL(EMI_ERR_RUNTIME, "internal: exchange tables inconsistent (%lld/%lld, %lld/%lld)", tl, P.lrows, tf, P.frows);
-    }
+    return 0;
   }
-  std::vector<double> lapin(N + 4, 0.0);  // RLAPIN(-1:N+2) (pre_suleg_mod.F90:64-69)
-  for (int n = 1; n <= N + 2; n++) lapin[n + 1] = -(P.ra * P.ra / (double)(n * (n + 1)));
-
-  phase("distribution + index tables");
-  // ---- Legendre panels of the local wavenumbers: PS[k][j] = P_{m+2k}^m(mu_{isl0+j}),
-  // PA[k][j] = P_{m+2k+1}^m, zero padded; plus the [j][k] transposed copy for the direct transform
-  void *dP = nullptr, *dPT = nullptr;
-  const size_t esz = P.esz;
-  if (emi_dev_malloc(&dP, (size_t)P.p_elems * esz) || emi_dev_malloc(&dPT, (size_t)P.pt_elems * esz)) {
-    delete pp;
-    EMI_FAIL(EMI_ERR_RUNTIME, "cannot allocate %.2f GiB for the Legendre panels", (P.p_elems + P.pt_elems) * (double)esz / (1 << 30));
+  auto band_of = [&](int lat) { return (int)(std::upper_bound(P.latlo.begin(), P.latlo.end(), lat) - P.latlo.begin()) - 1; };
+  for (int ml = 1; ml < NU; ml++)
+    if (P.mval[ml] <= P.mval[ml - 1]) EMI_FAIL(EMI_ERR_RUNTIME, "internal: local wavenumbers not ascending");
+  // Legendre side: block d holds the rows (lat in band d, local wavenumber ml with m <= NMEN(lat))
+  for (int ml = 0; ml < NU; ml++) {
+    const int m = P.mval[ml];
+    for (int lat = 0; lat < L; lat++)
+      if (P.nmen[lat] >= m) P.leg_rows[band_of(lat)]++;
   }
-  P.d_P = (char *)dP;
-  P.d_PT = (char *)dPT;
-  P.dev_allocs.push_back(dP);
-  P.dev_allocs.push_back(dPT);
-  // m >= 2: k_legpol on the device (below, once the device tables exist); m = 0, 1 (ordinary Legendre
-  // recurrence, supolf_mod.F90:124-142) on the host.  EMI_LEGPOL_HOST=1 computes every panel on the
-  // host threads instead (the two paths agree bit for bit, tests/test_gpu_parity.py).
-  // With CDIO_LEGPOL = readf / membuf every panel is taken from the file or segment instead (read_legpol_mod.F90:120-215).
-  const bool belousov = cfg->lduserpnm != 0 && !lp_read;  // LDUSERPNM: SUPOL per latitude on the host threads
-  const bool legpol_host = lp_read || belousov || (getenv("EMI_LEGPOL_HOST") && atoi(getenv("EMI_LEGPOL_HOST")));
-  std::vector<std::vector<double>> belpan;  // [ml] the panels [par][k][j] filled latitude by latitude
-  if (belousov) {
-    const int nmaxb = N + 1;  // INSMAX = NTMAX + 1 (suleg_mod.F90:402-410)
-    const emi::BelousovTables BT = emi::belousov_tables(nmaxb);
-    belpan.resize(NU);
-    for (int ml = 0; ml < NU; ml++) belpan[ml].assign((size_t)2 * (P.wrows[ml] / 2) * P.ldp[ml], 0.0);
-    emi::parallel_for(P.ndgnh, [&](int j) {
-      std::vector<double> pol((size_t)(nmaxb + 1) * (nmaxb + 1), 0.0);
-      emi::belousov_latitude(BT, P.rmu[j], pol.data());
-      for (int ml = 0; ml < NU; ml++) {
-        const int m = P.mval[ml], nd = P.lbase[ml + 1] - P.lbase[ml], isl0 = P.ndgnh - nd;
-        if (j < isl0) continue;
-        const int ld = P.ldp[ml], nk = P.wrows[ml] / 2;
-        double *pan = belpan[ml].data();
-        for (int par = 0; par < 2; par++)
-          for (int k = 0; m + 2 * k + par <= N + 1; k++)
-            pan[((size_t)par * nk + k) * ld + (j - isl0)] = pol[(size_t)m * (nmaxb + 1) + (m + 2 * k + par)];
-      }
-    });
-  }
-  if (emi_dev_memset(dP, 0, (size_t)P.p_elems * esz, 0) || emi_dev_memset(dPT, 0, (size_t)P.pt_elems * esz, 0)) {
-    delete pp;
-    return EMI_ERR_RUNTIME;
-  }
-  emi_stream_sync(0);
+  for (int d = 1; d < NP; d++) P.leg_disp[d] = P.leg_disp[d - 1] + P.leg_rows[d - 1];
   {
-    std::atomic<int> bad{0};
-    emi::parallel_for(NU, [&](int ml) {
-      const int m = P.mval[ml];
-      if (m >= 2 && !legpol_host) return;
+    // the local wavenumbers are ascending, so those present at a latitude are ml = 0 .. cnt-1 and the
+    // row of (lat, ml) is the first row of the latitude + ml
+    std::vector<long long> pos(P.leg_disp), latbase(L);
+    for (int lat = 0; lat < L; lat++) {
+      const int cnt = (int)(std::upper_bound(P.mval.begin(), P.mval.end(), P.nmen[lat]) - P.mval.begin());
+      latbase[lat] = pos[band_of(lat)];
+      pos[band_of(lat)] += cnt;
+    }
+    for (int ml = 0; ml < NU; ml++) {
       const int nd = P.lbase[ml + 1] - P.lbase[ml], isl0 = P.ndgnh - nd;
-      const int ld = P.ldp[ml], nk = P.wrows[ml] / 2;
-      const int nmax = N + 2;
-      std::vector<double> pan((size_t)2 * nk * ld, 0.0), col(nmax + 1);
-      std::vector<int> corr(nmax + 1);
-      if (belousov) {
-        pan.swap(belpan[ml]);
-      } else if (lp_read) {
-        // reference column c holds n descending: row k of the panel (n = m + 2k + par) is column nc-1-k
-        for (int par = 0; par < 2; par++) {
-          const int nc = par ? (N - m + 2) / 2 : (N - m + 3) / 2;
-          const char *mat = lp_src.base + (par ? lp_src.offA[m] : lp_src.offS[m]);
-          double *dst = pan.data() + (size_t)par * nk * ld;
-          for (int k = 0; k < nc; k++) memcpy(dst + (size_t)k * ld, mat + ((size_t)(nc - 1 - k) * nd) * 8, (size_t)nd * 8);
-        }
-      } else {
-        emi::LegCoef lc = emi::legendre_coefficients(m, nmax);
-        for (int j = 0; j < nd; j++) {
-          double mu = P.rmu[isl0 + j];
-          for (int par = 0; par < 2; par++) {
-            emi::legendre_column(lc, mu, par, col.data(), corr.data());
-            double *dst = pan.data() + (size_t)par * nk * ld;
-            for (int k = 0; m + 2 * k + par <= N + 1; k++) dst[(size_t)k * ld + j] = col[m + 2 * k + par];
-          }
-        }
+      for (int j = 0; j < nd; j++) {
+        legN[P.lbase[ml] + j] = (int)(latbase[isl0 + j] + ml);
+        legS[P.lbase[ml] + j] = (int)(latbase[L - 1 - isl0 - j] + ml);
       }
-      // the recurrences always run in double (as the reference's _sp build does: the JPRD work arrays of suleg_mod.F90:130-162);
-      // the fp32 library rounds the finished panel once
-      std::vector<float> cvt;
-      auto put = [&](char *dst, const std::vector<double> &v) {
-        if (esz == 8) return emi_h2d(dst, v.data(), v.size() * 8, 0);
-        cvt.resize(v.size());
-        for (size_t i = 0; i < v.size(); i++) cvt[i] = (float)v[i];
-        int rc = emi_h2d(dst, cvt.data(), cvt.size() * 4, 0);
-        emi_stream_sync(0);  // cvt is reused
-        return rc;
-      };
-      if (put(P.d_P + P.offS[ml] * esz, pan)) bad = 1;
-      const int ldk = P.ldk[ml], ndp = roundup(std::max(nd, 1), 16);  // = the panel extent behind offTA (pant)
-      std::vector<double> pt((size_t)2 * ndp * ldk, 0.0);
-      for (int par = 0; par < 2; par++)
-        for (int k = 0; k < nk; k++)
-          for (int j = 0; j < nd; j++) pt[((size_t)par * ndp + j) * ldk + k] = pan[((size_t)par * nk + k) * ld + j];
-      if (put(P.d_PT + P.offTS[ml] * esz, pt)) bad = 1;
-      emi_stream_sync(0);
-    });
-    if (bad) {
-      delete pp;
-      return EMI_ERR_RUNTIME;
     }
   }
-  phase("legendre panels (host part)");
-  // ---- device tables
-  int *d_mval, *d_nmen, *d_gpoff, *d_nasm0, *d_fbase, *d_fftrow, *d_lbase, *d_legN, *d_legS, *d_wbase, *d_wrows, *d_rowm, *d_ebase,
-      *d_ldp, *d_ldk, *d_ltp, *d_ktp;
-  double *d_eps, *d_lapin, *d_rw, *d_racthe, *d_specw;
-  long long *d_offS, *d_offA, *d_offTS, *d_offTA;
-  if (upload(P.mval, &d_mval) || upload(P.l_nmen, &d_nmen) || upload(P.l_gpoff, &d_gpoff) || upload(P.nasm0, &d_nasm0) ||
-      upload(P.l_fbase, &d_fbase) || upload(fftrow, &d_fftrow) || upload(P.lbase, &d_lbase) || upload(legN, &d_legN) ||
-      upload(legS, &d_legS) || upload(P.wbase, &d_wbase) || upload(P.wrows, &d_wrows) || upload(rowm, &d_rowm) ||
-      upload(ebase, &d_ebase) || upload(P.ldp, &d_ldp) || upload(P.ldk, &d_ldk) || upload(P.lattile_pref, &d_ltp) ||
-      upload(P.ktile_pref, &d_ktp) || upload(eps, &d_eps) || upload(lapin, &d_lapin) || upload(l_rw, &d_rw) ||
-      upload(l_racthe, &d_racthe) || upload(specw, &d_specw) || upload(P.offS, &d_offS) || upload(P.offA, &d_offA) ||
-      upload(P.offTS, &d_offTS) || upload(P.offTA, &d_offTA)) {
-    delete pp;
-    return EMI_ERR_RUNTIME;
+  // FFT side: block s holds the rows (local lat, wavenumber m of task s with m <= NMEN(lat)), same order
+  for (int m = 0; m <= N; m++)
+    for (int jl = 0; jl < NL; jl++)
+      if (P.l_nmen[jl] >= m) P.fft_rows[P.procm[m]]++;
+  for (int sr = 1; sr < NP; sr++) P.fft_disp[sr] = P.fft_disp[sr - 1] + P.fft_rows[sr - 1];
+  {
+    std::vector<long long> pos(P.fft_disp);
+    for (int jl = 0; jl < NL; jl++)
+      for (int m = 0; m <= P.l_nmen[jl]; m++) fftrow[P.l_fbase[jl] + m] = (int)pos[P.procm[m]]++;
   }
-  for (void *p : {(void *)d_mval, (void *)d_nmen, (void *)d_gpoff, (void *)d_nasm0, (void *)d_fbase, (void *)d_fftrow, (void *)d_lbase,
-                  (void *)d_legN, (void *)d_legS, (void *)d_wbase, (void *)d_wrows, (void *)d_rowm, (void *)d_ebase, (void *)d_ldp,
-                  (void *)d_ldk, (void *)d_ltp, (void *)d_ktp, (void *)d_eps, (void *)d_lapin, (void *)d_rw, (void *)d_racthe,
-                  (void *)d_specw, (void *)d_offS, (void *)d_offA, (void *)d_offTS, (void *)d_offTA})
-    P.dev_allocs.push_back(p);
+  long long tl = 0, tf = 0;
+  for (int r = 0; r < NP; r++) tl += P.leg_rows[r], tf += P.fft_rows[r];
+  if (tl != P.lrows || tf != P.frows) EMI_FAIL(EMI_ERR_RUNTIME, "internal: exchange tables inconsistent (%lld/%lld, %lld/%lld)", tl, P.lrows, tf, P.frows);
+  return 0;
+}
+
+// ---- stage 6: the Legendre panels of the local wavenumbers, host part: PS[k][j] = P_{m+2k}^m(mu_{isl0+j}),
+// PA[k][j] = P_{m+2k+1}^m, zero padded; plus the [j][k] transposed copy for the direct transform.
+// A panel of wavenumber ml on the host is [par][k][j], k < wrows / 2, j < ldp; three ways to fill one:
+// CDIO_LEGPOL = readf / membuf: from the file or segment (read_legpol_mod.F90:120-215)
+static void panel_from_source(const Plan &P, const LegpolSource &src, int ml, std::vector<double> &pan) {
+  const int N = P.nsmax, m = P.mval[ml], nd = P.lbase[ml + 1] - P.lbase[ml], ld = P.ldp[ml], nk = P.wrows[ml] / 2;
+  // reference column c holds n descending: row k of the panel (n = m + 2k + par) is column nc-1-k
+  for (int par = 0; par < 2; par++) {
+    const int nc = par ? (N - m + 2) / 2 : (N - m + 3) / 2;
+    const char *mat = src.base + (par ? src.offA[m] : src.offS[m]);
+    double *dst = pan.data() + (size_t)par * nk * ld;
+    for (int k = 0; k < nc; k++) memcpy(dst + (size_t)k * ld, mat + ((size_t)(nc - 1 - k) * nd) * 8, (size_t)nd * 8);
+  }
+}
+// LDUSERPNM: SUPOL per latitude on the host threads, every panel [ml] filled latitude by latitude
+static void panels_belousov(const Plan &P, std::vector<std::vector<double>> &pans) {
+  const int N = P.nsmax, NU = P.nump;
+  const int nmaxb = N + 1;  // INSMAX = NTMAX + 1 (suleg_mod.F90:402-410)
+  const emi::BelousovTables BT = emi::belousov_tables(nmaxb);
+  pans.resize(NU);
+  for (int ml = 0; ml < NU; ml++) pans[ml].assign((size_t)2 * (P.wrows[ml] / 2) * P.ldp[ml], 0.0);
+  emi::parallel_for(P.ndgnh, [&](int j) {
+    std::vector<double> pol((size_t)(nmaxb + 1) * (nmaxb + 1), 0.0);
+    emi::belousov_latitude(BT, P.rmu[j], pol.data());
+    for (int ml = 0; ml < NU; ml++) {
+      const int m = P.mval[ml], nd = P.lbase[ml + 1] - P.lbase[ml], isl0 = P.ndgnh - nd;
+      if (j < isl0) continue;
+      const int ld = P.ldp[ml], nk = P.wrows[ml] / 2;
+      double *pan = pans[ml].data();
+      for (int par = 0; par < 2; par++)
+        for (int k = 0; m + 2 * k + par <= N + 1; k++)
+          pan[((size_t)par * nk + k) * ld + (j - isl0)] = pol[(size_t)m * (nmaxb + 1) + (m + 2 * k + par)];
+    }
+  });
+}
+// the ordinary Legendre recurrence (supolf_mod.F90:124-142), what k_legpol computes on the device
+static void panel_by_recurrence(const Plan &P, int ml, std::vector<double> &pan) {
+  const int N = P.nsmax, m = P.mval[ml], nd = P.lbase[ml + 1] - P.lbase[ml], isl0 = P.ndgnh - nd, ld = P.ldp[ml], nk = P.wrows[ml] / 2;
+  const int nmax = N + 2;
+  std::vector<double> col(nmax + 1);
+  std::vector<int> corr(nmax + 1);
+  emi::LegCoef lc = emi::legendre_coefficients(m, nmax);
+  for (int j = 0; j < nd; j++) {
+    double mu = P.rmu[isl0 + j];
+    for (int par = 0; par < 2; par++) {
+      emi::legendre_column(lc, mu, par, col.data(), corr.data());
+      double *dst = pan.data() + (size_t)par * nk * ld;
+      for (int k = 0; m + 2 * k + par <= N + 1; k++) dst[(size_t)k * ld + j] = col[m + 2 * k + par];
+    }
+  }
+}
+// Allocates the two panel arrays and fills what the host fills: m = 0, 1 by the recurrence, m >= 2 left to k_legpol (stage 8, once
+// the device tables exist) unless `all_m`: every panel from `src` when there is one, else by SUPOL when `belousov`, else by the
+// recurrence (EMI_LEGPOL_HOST=1; the host and the device recurrence agree bit for bit, tests/test_gpu_parity.py).
+static int setup_panels_host(Plan &P, const LegpolSource *src, bool belousov, bool all_m) {
+  const size_t esz = P.esz;
+  if (P.dev_allocs.alloc((void **)&P.d_P, (size_t)P.p_elems * esz) || P.dev_allocs.alloc((void **)&P.d_PT, (size_t)P.pt_elems * esz))
+    EMI_FAIL(EMI_ERR_RUNTIME, "cannot allocate %.2f GiB for the Legendre panels", (P.p_elems + P.pt_elems) * (double)esz / (1 << 30));
+  std::vector<std::vector<double>> belpan;
+  if (belousov) panels_belousov(P, belpan);
+  if (emi_dev_memset(P.d_P, 0, (size_t)P.p_elems * esz, 0) || emi_dev_memset(P.d_PT, 0, (size_t)P.pt_elems * esz, 0)) return EMI_ERR_RUNTIME;
+  emi_stream_sync(0);
+  std::atomic<int> bad{0};
+  emi::parallel_for(P.nump, [&](int ml) {
+    if (P.mval[ml] >= 2 && !all_m) return;
+    const int nd = P.lbase[ml + 1] - P.lbase[ml], ld = P.ldp[ml], nk = P.wrows[ml] / 2;
+    std::vector<double> pan((size_t)2 * nk * ld, 0.0);
+    if (belousov)
+      pan.swap(belpan[ml]);
+    else if (src)
+      panel_from_source(P, *src, ml, pan);
+    else
+      panel_by_recurrence(P, ml, pan);
+    // the recurrences always run in double (as the reference's _sp build does: the JPRD work arrays of suleg_mod.F90:130-162);
+    // the fp32 library rounds the finished panel once
+    std::vector<float> cvt;
+    auto put = [&](char *dst, const std::vector<double> &v) {
+      if (esz == 8) return emi_h2d(dst, v.data(), v.size() * 8, 0);
+      cvt.resize(v.size());
+      for (size_t i = 0; i < v.size(); i++) cvt[i] = (float)v[i];
+      int rc = emi_h2d(dst, cvt.data(), cvt.size() * 4, 0);
+      emi_stream_sync(0);  // cvt is reused
+      return rc;
+    };
+    if (put(P.d_P + P.offS[ml] * esz, pan)) bad = 1;
+    const int ldk = P.ldk[ml], ndp = roundup(std::max(nd, 1), 16);  // = the panel extent behind offTA (pant)
+    std::vector<double> pt((size_t)2 * ndp * ldk, 0.0);
+    for (int par = 0; par < 2; par++)
+      for (int k = 0; k < nk; k++)
+        for (int j = 0; j < nd; j++) pt[((size_t)par * ndp + j) * ldk + k] = pan[((size_t)par * nk + k) * ld + j];
+    if (put(P.d_PT + P.offTS[ml] * esz, pt)) bad = 1;
+    emi_stream_sync(0);
+  });
+  return bad ? EMI_ERR_RUNTIME : 0;
+}
+
+// stage 7: the device tables of P.g
+static int setup_device_tables(Plan &P, const SetupTables &T) {
   EmiGeomDev &g = P.g;
-  g.nsmax = N;
-  g.nump = NU;
-  g.nlat = NL;
+  g.nsmax = P.nsmax;
+  g.nump = P.nump;
+  g.nlat = P.nlat;
   g.ngptot = P.ngptot;
   g.m0_wide = P.esz == 4 ? 1 : 0;  // the fp32 library computes zonal wavenumber 0 in double (ledir_mod.F90:133-171)
-  g.mval = d_mval;
-  g.nmen = d_nmen;
-  g.gpoff = d_gpoff;
-  g.nasm0 = d_nasm0;
-  g.fbase = d_fbase;
-  g.fftrow = tables ? d_fftrow : nullptr;  // one task: rows are fbase[lat] + m, no table
-  g.lbase = d_lbase;
-  g.legN = d_legN;
-  g.legS = d_legS;
-  g.wbase = d_wbase;
-  g.wrows = d_wrows;
-  g.rowm = d_rowm;
-  g.ebase = d_ebase;
-  g.eps = d_eps;
-  g.lapin = d_lapin;
-  g.rw = d_rw;
-  g.racthe = d_racthe;
   g.P = P.d_P;
-  g.offS = d_offS;
-  g.offA = d_offA;
-  g.ldp = d_ldp;
   g.PT = P.d_PT;
-  g.offTS = d_offTS;
-  g.offTA = d_offTA;
-  g.ldk = d_ldk;
-  g.lattile_pref = d_ltp;
-  g.ktile_pref = d_ktp;
-  g.specw = d_specw;
-  phase("device tables");
-  if (!legpol_host) {
-    // ---- Legendre panels, m >= 2: one thread per (wavenumber, parity, latitude)
-    const int nmax = N + 2;
-    std::vector<double> dcl((size_t)NU * (nmax + 1), 0.0), ddl((size_t)NU * (nmax + 1), 0.0), zf(NU, 0.0), mu(P.rmu.begin(), P.rmu.begin() + P.ndgnh);
-    std::vector<int> blk;
-    emi::parallel_for(NU, [&](int ml) {
-      if (P.mval[ml] < 2) return;
-      emi::LegCoef lc = emi::legendre_coefficients(P.mval[ml], nmax);
-      std::copy(lc.dcl.begin(), lc.dcl.end(), dcl.begin() + (size_t)ml * (nmax + 1));
-      std::copy(lc.ddl.begin(), lc.ddl.end(), ddl.begin() + (size_t)ml * (nmax + 1));
-      zf[ml] = lc.zfac_m;
-    });
-    for (int ml = 0; ml < NU; ml++) {  // m ascending = longest recurrences first
-      if (P.mval[ml] < 2) continue;
-      const int nd = P.lbase[ml + 1] - P.lbase[ml];
-      for (int par = 0; par < 2; par++)
-        for (int jt = 0; jt * 64 < nd; jt++) {
-          blk.push_back(ml);
-          blk.push_back(par << 16 | jt);
-        }
-    }
-    if (!blk.empty()) {
-      double *d_dcl, *d_ddl, *d_zf, *d_mu;
-      int *d_blk;
-      if (upload(dcl, &d_dcl) || upload(ddl, &d_ddl) || upload(zf, &d_zf) || upload(mu, &d_mu) || upload(blk, &d_blk)) {
-        delete pp;
-        return EMI_ERR_RUNTIME;
+  if (upload(P.dev_allocs, P.mval, &g.mval) || upload(P.dev_allocs, P.l_nmen, &g.nmen) || upload(P.dev_allocs, P.l_gpoff, &g.gpoff) || upload(P.dev_allocs, P.nasm0, &g.nasm0) ||
+      upload(P.dev_allocs, P.l_fbase, &g.fbase) || upload(P.dev_allocs, T.fftrow, &g.fftrow) || upload(P.dev_allocs, P.lbase, &g.lbase) || upload(P.dev_allocs, T.legN, &g.legN) ||
+      upload(P.dev_allocs, T.legS, &g.legS) || upload(P.dev_allocs, P.wbase, &g.wbase) || upload(P.dev_allocs, P.wrows, &g.wrows) || upload(P.dev_allocs, T.rowm, &g.rowm) ||
+      upload(P.dev_allocs, T.ebase, &g.ebase) || upload(P.dev_allocs, P.ldp, &g.ldp) || upload(P.dev_allocs, P.ldk, &g.ldk) || upload(P.dev_allocs, P.lattile_pref, &g.lattile_pref) ||
+      upload(P.dev_allocs, P.ktile_pref, &g.ktile_pref) || upload(P.dev_allocs, T.eps, &g.eps) || upload(P.dev_allocs, T.lapin, &g.lapin) || upload(P.dev_allocs, T.l_rw, &g.rw) ||
+      upload(P.dev_allocs, T.l_racthe, &g.racthe) || upload(P.dev_allocs, T.specw, &g.specw) || upload(P.dev_allocs, P.offS, &g.offS) || upload(P.dev_allocs, P.offA, &g.offA) ||
+      upload(P.dev_allocs, P.offTS, &g.offTS) || upload(P.dev_allocs, P.offTA, &g.offTA))
+    return EMI_ERR_RUNTIME;
+  if (!T.rowtable) g.fftrow = nullptr;  // one task: rows are fbase[lat] + m, no table (the upload stays the plan's)
+  return 0;
+}
+
+// stage 8: the Legendre panels of m >= 2 on the device: one thread per (wavenumber, parity, latitude)
+static int setup_panels_device(Plan &P) {
+  const int NU = P.nump, nmax = P.nsmax + 2;
+  std::vector<double> dcl((size_t)NU * (nmax + 1), 0.0), ddl((size_t)NU * (nmax + 1), 0.0), zf(NU, 0.0), mu(P.rmu.begin(), P.rmu.begin() + P.ndgnh);
+  std::vector<int> blk;
+  emi::parallel_for(NU, [&](int ml) {
+    if (P.mval[ml] < 2) return;
+    emi::LegCoef lc = emi::legendre_coefficients(P.mval[ml], nmax);
+    std::copy(lc.dcl.begin(), lc.dcl.end(), dcl.begin() + (size_t)ml * (nmax + 1));
+    std::copy(lc.ddl.begin(), lc.ddl.end(), ddl.begin() + (size_t)ml * (nmax + 1));
+    zf[ml] = lc.zfac_m;
+  });
+  for (int ml = 0; ml < NU; ml++) {  // m ascending = longest recurrences first
+    if (P.mval[ml] < 2) continue;
+    const int nd = P.lbase[ml + 1] - P.lbase[ml];
+    for (int par = 0; par < 2; par++)
+      for (int jt = 0; jt * 64 < nd; jt++) {
+        blk.push_back(ml);
+        blk.push_back(par << 16 | jt);
       }
-      LegPolDev la{d_mu, d_dcl, d_ddl, d_zf, d_blk, P.ndgnh, nmax};
-      EmiRange rg_suleg(EMI_LBL_SULEG);  // GSTATS 140
-      EMI_LAUNCH_P(P.esz, k_legpol, blk.size() / 2, 64, 0, (emi_stream_t)0, P.g, la);
-      emi_stream_sync(0);
-      for (void *q : {(void *)d_dcl, (void *)d_ddl, (void *)d_zf, (void *)d_mu, (void *)d_blk}) emi_dev_free(q);
-    }
-    phase("legendre panels (device)");
   }
-  int rc = build_fft_plans(P);
-  phase("fft plans + tables");
-  if (rc) {
-    delete pp;
-    return rc;
-  }
+  if (blk.empty()) return 0;
+  DevAllocs tmp;  // the kernel's inputs live for this stage only
+  LegPolDev la{};
+  la.ndgnh = P.ndgnh;
+  la.nmax = nmax;
+  if (upload(tmp, dcl, &la.dcl) || upload(tmp, ddl, &la.ddl) || upload(tmp, zf, &la.zfac) || upload(tmp, mu, &la.mu) || upload(tmp, blk, &la.blk)) return EMI_ERR_RUNTIME;
+  EmiRange rg_suleg(EMI_LBL_SULEG);  // GSTATS 140
+  EMI_LAUNCH_P(P.esz, k_legpol, blk.size() / 2, 64, 0, (emi_stream_t)0, P.g, la);
   emi_stream_sync(0);
-  P.active = true;
-  if (G.plans[slot]) delete G.plans[slot];
-  G.plans[slot] = pp;
+  return 0;
+}
+
+static int first_free_slot() {
+  for (int i = 0; i < G.max_resol; i++)
+    if (!G.plans[i]) return i;
+  return -1;
+}
+
+extern "C" int emi_setup_legpol(const emi_setup_t *cfg, const emi_legpol_io_t *io, int *kresol) {
+  EmiRange rg_setup(EMI_LBL_SETUP);  // GSTATS 2
+  LegpolMode lp_mode;
+  if (int rc = setup_arguments(cfg, io, &lp_mode)) return rc;
+  LegpolSource lp_src;
+  if ((lp_mode == LP_READF || lp_mode == LP_MEMBUF) && legpol_open(lp_src, io, lp_mode == LP_MEMBUF)) return EMI_ERR_ARG;
+  const bool lp_read = lp_src.base != nullptr;
+  const int slot = first_free_slot();
+  if (slot < 0) EMI_FAIL(EMI_ERR_STATE, "SETUP_TRANS:IDEF_RESOL > NMAX_RESOL");
+  std::unique_ptr<Plan> pp(new Plan());  // whatever exit is taken from here on, the plan frees what it has allocated
+  Plan &P = *pp;
+  P.nsmax = cfg->ksmax;
+  P.ndgl = cfg->kdgl;
+  P.ndgnh = (P.ndgl + 1) / 2;
+  P.ra = G.ra;
+  P.esz = cfg->precision == 4 ? 4 : 8;
+  P.nproc = G.nproc;
+  P.me = G.myproc - 1;
+  P.nprv = G.nprtrv;
+  P.mev = G.mysetv - 1;
+  if (G.nproc_all > 1 && !G.a2a) EMI_FAIL(EMI_ERR_STATE, "SETUP_TRANS: %d tasks but no all-to-all-v hook registered (emi_set_alltoallv)", G.nproc_all);
+  if (P.nproc > P.ndgl / 2 || P.nproc > P.nsmax + 1) EMI_FAIL(EMI_ERR_ARG, "SETUP_TRANS: too many tasks (%d) for NDGL=%d, NSMAX=%d", P.nproc, P.ndgl, P.nsmax);
+  int rc;
+  std::vector<long long> cum;  // [NDGL + 1] grid points before every latitude
+  SetupTables T;
+  SetupClock clock;
+  if ((rc = setup_geometry(cfg, P, cum))) return rc;
+  clock.phase("gaussian latitudes");
+  if (lp_read && legpol_index(lp_src, P.nsmax, P.ndgnh, P.nloen, P.nmen, P.ndglu)) return EMI_ERR_ARG;
+  if ((rc = setup_distribution(P.nsmax, P.ndgl, P.nloen, cum, P.nproc, P.nprv, P.procm, P.latlo, P.vlat))) return rc;
+  setup_local_tables(P, cum, T);
+  if ((rc = setup_row_tables(P, P.nproc > 1 || (test_paths() & 1), T))) return rc;
+  clock.phase("distribution + index tables");
+  const bool belousov = cfg->lduserpnm != 0 && !lp_read;
+  const bool legpol_host = lp_read || belousov || (getenv("EMI_LEGPOL_HOST") && atoi(getenv("EMI_LEGPOL_HOST")));
+  if ((rc = setup_panels_host(P, lp_read ? &lp_src : nullptr, belousov, legpol_host))) return rc;
+  clock.phase("legendre panels (host part)");
+  if ((rc = setup_device_tables(P, T))) return rc;
+  clock.phase("device tables");
+  if (!legpol_host) {
+    if ((rc = setup_panels_device(P))) return rc;
+    clock.phase("legendre panels (device)");
+  }
+  rc = build_fft_plans(P);
+  clock.phase("fft plans + tables");
+  if (rc) return rc;
+  emi_stream_sync(0);
+  G.plans[slot] = std::move(pp);
   if (kresol) *kresol = slot + 1;
   if (lp_mode == LP_WRITEF) {  // suleg_mod.F90:1186
     rc = legpol_write(slot + 1, io->fname);
-    phase("legendre file written");
+    clock.phase("legendre file written");
     if (rc) {
       emi_release(slot + 1);
       return rc;
@@ -1539,24 +1538,7 @@ extern "C" int emi_release(int kresol) {
   if (!P) EMI_FAIL(EMI_ERR_STATE, "TRANS_RELEASE: unknown resolution %d", kresol);
   plan_quiesce(*P);
   emi_stream_sync(0);
-#ifndef EMI_CPU_EMU
-  if (P->ev_done) (void)hipEventDestroy(P->ev_done);
-#endif
-  for (void *p : P->dev_allocs) emi_dev_free(p);
-  for (auto &kv : P->legmaps) {
-    emi_dev_free(kv.second.d_inv);
-    emi_dev_free(kv.second.d_inv_wide);
-    emi_dev_free(kv.second.d_dir_wide);
-    emi_dev_free(kv.second.d_dir);
-  }
-  emi_dev_free(P->d_W);
-  emi_dev_free(P->d_FBL);
-  if (P->d_FBF != P->d_FBL) emi_dev_free(P->d_FBF);
-  emi_dev_free(P->d_desc);
-  emi_dev_free(P->d_fftscr);
-  P->active = false;
-  delete P;
-  G.plans[kresol - 1] = nullptr;
+  G.plans[kresol - 1].reset();
   emi_stage::trim();  // the idle staging buffers of host-array calls were sized for this resolution
   return EMI_SUCCESS;
 }
@@ -1573,7 +1555,7 @@ extern "C" int emi_trim_cache(void) {
 extern "C" int emi_finalize(void) {
   if (!G.init) return EMI_SUCCESS;
   for (int i = 0; i < (int)G.plans.size(); i++)
-    if (G.plans[i] && G.plans[i]->active) emi_release(i + 1);
+    if (G.plans[i]) emi_release(i + 1);
   G.plans.clear();
   emi_stage::trim();
   G.init = false;
@@ -1991,7 +1973,7 @@ static int ensure_desc(Plan &P, size_t bytes) {
 // wavenumber groups of 4 / 2 / 1 XCDs -- fetched bytes go up, time never down; row tiles innermost -- 10 % fewer
 // bytes for k_leg_dir and 1.4 % more time.)
 // which: 0 every wavenumber, 1 all but the wide one (fp32 library: m = 0 accumulates in double and has a kernel of its own), 2 only that one
-static int build_tilemap(const Plan &P, const std::vector<int> &pref, int nct, int2 **d_map, long long *nblocks, int which = 0) {
+static int build_tilemap(Plan &P, const std::vector<int> &pref, int nct, int2 **d_map, long long *nblocks, int which = 0) {
   const int nx = 8;  // XCDs
   int gx = 1;
   while (gx * 2 <= std::min(nct, nx)) gx *= 2;
@@ -2021,7 +2003,7 @@ static int build_tilemap(const Plan &P, const std::vector<int> &pref, int nct, i
     *d_map = nullptr;
     return 0;
   }
-  return upload(map, d_map);
+  return upload(P.dev_allocs, map, d_map);
 }
 
 static int leg_tilemaps(Plan &P, int nct, LegMaps **out) {
@@ -3688,8 +3670,8 @@ extern "C" int emi_wait(int kresol) {
     return EMI_SUCCESS;
   }
   for (size_t i = 0; i < G.plans.size(); i++) {
-    Plan *Pp = G.plans[i];
-    if (!Pp || !Pp->active) continue;
+    Plan *Pp = G.plans[i].get();
+    if (!Pp) continue;
     if (const int rc = plan_quiesce(*Pp)) EMI_FAIL(EMI_ERR_RUNTIME, "emi_wait: the last call of resolution %d did not complete (%s)", (int)i, emi_rt_errstr(rc));
   }
   return EMI_SUCCESS;

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from oracle.oracle import Oracle
-from tests.common import adjoint_case, closed_form_errors, legpol_io_case, octahedral, run_case, utility_case
+from tests.common import adjoint_case, closed_form_errors, legpol_io_case, octahedral, random_spectrum, rel_err, run_case, utility_case
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 1e-12  # fp64: observed ~1e-15
@@ -365,6 +365,46 @@ def test_argument_errors_mirror_abort_trans(et):
     et.trans_release(r)
     with pytest.raises(et.TransError, match="unknown resolution"):
         et.trans_inq(r, "nspec2")
+
+
+def test_resolution_numbers_are_taken_released_and_reused(et):
+    """The slots of SETUP_TRANS0's KMAX_RESOL: a refused SETUP_TRANS takes no resolution number, successful ones number
+    1, 2, ..., the one after KMAX_RESOL is refused, a released number is the next one given out, and a released number
+    is unknown to the transforms and inquiries."""
+    N = 8
+    nloen = octahedral(N)
+    kmax, _ = et.inq_init()
+    with pytest.raises(et.TransError, match="KDGL IS NOT A POSITIVE, EVEN NUMBER"):
+        et.setup_trans(N, 17, nloen[:17])
+    rs = [et.setup_trans(N, len(nloen), nloen) for _ in range(kmax)]
+    try:
+        assert rs == list(range(1, kmax + 1))
+        with pytest.raises(et.TransError, match="SETUP_TRANS:IDEF_RESOL > NMAX_RESOL"):
+            et.setup_trans(N, len(nloen), nloen)
+        gone = rs[kmax // 2]
+        ns2, ng = et.trans_inq(gone, "nspec2"), et.trans_inq(gone, "ngptot")
+        et.trans_release(gone)
+        with pytest.raises(et.TransError, match="unknown resolution"):
+            et.trans_inq(gone, "nspec2")
+        with pytest.raises(et.TransError, match="unknown resolution"):
+            et.inv_trans(gone, pspscalar=np.zeros((ns2, 1)), pgp=np.zeros((1, 1, ng)))
+        with pytest.raises(et.TransError, match="unknown resolution"):
+            et.trans_release(gone)
+        rs.remove(gone)
+        # the freed number, with another grid and truncation: what is set up there is the new resolution
+        nloen2 = octahedral(N + 3)
+        again = et.setup_trans(N + 3, len(nloen2), nloen2)
+        rs.append(again)
+        assert again == gone
+        o = Oracle(N + 3, nloen2)
+        assert (et.trans_inq(again, "nspec2"), et.trans_inq(again, "ngptot")) == (o.nspec2, o.ngptot)
+        sc = random_spectrum(np.random.default_rng(11), o.nasm0, N + 3, o.nspec2, 2, False)
+        gp = np.zeros((1, 2, o.ngptot))
+        et.inv_trans(again, pspscalar=sc, pgp=gp)
+        assert rel_err(gp[0], o.inv_trans(spsc=sc), axis=1) < TOL
+    finally:
+        for r in rs:
+            et.trans_release(r)
 
 
 def test_array_extent_checks_mirror_abort_trans(et):
