@@ -51,7 +51,7 @@ class _LegpolIO(C.Structure):
 class _Setup(C.Structure):
     _fields_ = [("ksmax", C.c_int), ("kdgl", C.c_int), ("kloen", C.POINTER(C.c_int)), ("kdlon", C.c_int),
                 ("precision", C.c_int), ("lduseflt", C.c_int), ("ldll", C.c_int), ("ldstretch", C.c_int),
-                ("lduserpnm", C.c_int)]
+                ("lduserpnm", C.c_int), ("ldshiftll", C.c_int)]
 
 
 class _Ext(C.Structure):  # emi_extents_t
@@ -66,7 +66,8 @@ class _Inv(C.Structure):
                 ("spsc2", C.c_void_p), ("nf_sc2", C.c_int), ("ldscders", C.c_int), ("ldvorgp", C.c_int),
                 ("lddivgp", C.c_int), ("lduvder", C.c_int), ("kproma", C.c_int), ("gp", C.c_void_p),
                 ("gp_nfld", C.c_int), ("gpuv", C.c_void_p), ("gp3a", C.c_void_p), ("gp3b", C.c_void_p),
-                ("gp2", C.c_void_p), ("stream", C.c_void_p), ("ext", C.POINTER(_Ext)), ("vsets", C.POINTER(_VSets))]
+                ("gp2", C.c_void_p), ("stream", C.c_void_p), ("ext", C.POINTER(_Ext)), ("vsets", C.POINTER(_VSets)),
+                ("ldlatlon", C.c_int)]
 
 
 class _Dir(C.Structure):
@@ -253,7 +254,8 @@ _PREC = {}  # kresol -> array dtype name of that resolution
 
 
 def setup_trans(ksmax, kdgl, kloen=None, kdlon=0, lduseflt=False, ldll=False, pstret=None, precision=8,
-                cdio_legpol=None, cdlegpolfname=None, klegpolptr=None, klegpolptr_len=None, lduserpnm=False):
+                cdio_legpol=None, cdlegpolfname=None, klegpolptr=None, klegpolptr_len=None, lduserpnm=False,
+                ldshiftll=False):
     """SETUP_TRANS (setup_trans.h:12-115); returns KRESOL.
 
     cdio_legpol: "writef" writes the Legendre polynomials of this setup to `cdlegpolfname`, "readf" takes
@@ -262,7 +264,12 @@ def setup_trans(ksmax, kdgl, kloen=None, kdlon=0, lduseflt=False, ldll=False, ps
 
     precision: 8 = the reference's double-precision library (libtrans_dp, JPRB=JPRD), arrays are
     float64; 4 = its single-precision library (libtrans_sp, JPRB=JPRM), arrays are float32 (setup --
-    Gaussian latitudes, Legendre recurrences -- still runs in double, as in the reference)."""
+    Gaussian latitudes, Legendre recurrences -- still runs in double, as in the reference).
+
+    ldll: a regular latitude-longitude grid for ``inv_trans(..., ldlatlon=True)`` with the reference's argument conventions
+    (setup_trans.F90:258-271): ``kdlon`` = nlon; unshifted, ``kdgl`` = nlat - 1 (nlat odd) and the handle has NDGL = kdgl + 2
+    rows, pole to pole with the equator held twice; ``ldshiftll``: ``kdgl`` = nlat (even), rows and longitudes offset by half a
+    cell.  The series is evaluated exactly on those rows.  Such a handle serves no other transform."""
     if precision not in (4, 8):
         raise TransError("SETUP_TRANS: precision must be 4 or 8")
     cfg = _Setup()
@@ -274,6 +281,7 @@ def setup_trans(ksmax, kdgl, kloen=None, kdlon=0, lduseflt=False, ldll=False, ps
             raise TransError("SETUP_TRANS: KLOEN TOO SHORT")
         cfg.kloen = keep.ctypes.data_as(C.POINTER(C.c_int))
     cfg.lduseflt, cfg.ldll = int(bool(lduseflt)), int(bool(ldll))
+    cfg.ldshiftll = int(bool(ldshiftll))
     cfg.lduserpnm = int(bool(lduserpnm))  # True: Belousov's generator (the Fortran API's default); False: SUPOLF, as the benchmark
     cfg.ldstretch = int(pstret is not None and abs(pstret - 1.0) > 100 * np.finfo(float).eps)
     kresol = C.c_int(0)
@@ -301,7 +309,8 @@ def real_dtype(kresol):
 
 
 _INT_SCALARS = ("nspec2", "nspec2g", "nspec2mx", "nspec", "nspecg", "ngptot", "ngptotg", "ngptotmx", "nump", "ndgl",
-                "nsmax", "ndlon", "nproc", "myproc", "nfrstlat", "nlstlat", "nprtrw", "nprtrv", "mysetw", "mysetv", "ngptot_band")
+                "nsmax", "ndlon", "nproc", "myproc", "nfrstlat", "nlstlat", "nprtrw", "nprtrv", "mysetw", "mysetv", "ngptot_band",
+                "ldll", "lshiftll")
 _INT_ARRAYS = {"nloen": "ndgl", "nmen": "ndgl", "ndglu": "nsmax+1", "nasm0": "nsmax+1", "myms": "nump",
                "procm": "nsmax+1", "latlo": "nproc+1", "fftwork": "ndgl"}
 _REAL_ARRAYS = {"rmu": "ndgl", "pmu": "ndgl", "rgw": "ndgl", "pgw": "ndgl", "racthe": "ndgl"}
@@ -410,8 +419,10 @@ def _fill_vsets(a, keep, kvsetuv, kvsetsc, kvsetsc2, kvsetsc3a, kvsetsc3b, pgp3a
 def inv_trans(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, pspsc3b=None, pspsc2=None,
               ldscders=False, ldvorgp=False, lddivgp=False, lduvder=False, kproma=None, pgp=None, pgpuv=None,
               pgp3a=None, pgp3b=None, pgp2=None, stream=None, kvsetuv=None, kvsetsc=None, kvsetsc2=None, kvsetsc3a=None,
-              kvsetsc3b=None):
-    """INV_TRANS (inv_trans.h:12-163): spectral -> grid point, results written into pgp*/..."""
+              kvsetsc3b=None, ldlatlon=False):
+    """INV_TRANS (inv_trans.h:12-163): spectral -> grid point, results written into pgp*/...
+
+    ldlatlon: the output is the lat-lon grid of a handle set up with ``ldll`` (required there, refused elsewhere)."""
     a, space, keep = _Inv(), [None, real_dtype(kresol)], []
     nspec2, ngptot = trans_inq(kresol, "nspec2"), trans_inq(kresol, "ngptot")
     nproma = int(kproma) if kproma else ngptot
@@ -421,6 +432,7 @@ def inv_trans(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, ps
                (pspvor, pspdiv, pspscalar, pspsc3a, pspsc3b, pspsc2))
     a.ldscders, a.ldvorgp, a.lddivgp, a.lduvder = int(ldscders), int(ldvorgp), int(lddivgp), int(lduvder)
     a.kproma = nproma
+    a.ldlatlon = int(bool(ldlatlon))
     a.mem_space = space[0] if space[0] is not None else EMI_MEM_HOST
     a.stream = stream
     _fill_vsets(a, keep, kvsetuv, kvsetsc, kvsetsc2, kvsetsc3a, kvsetsc3b, pgp3a, pgp3b, 3 if ldscders else 1)

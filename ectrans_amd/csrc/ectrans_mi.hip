@@ -286,6 +286,9 @@ struct Plan {  // owns its device memory; whoever drops a plan that has run some
   ~Plan();
   int nsmax = 0, ndgl = 0, ndgnh = 0;
   bool reduced = false;
+  // LDLL: a regular lat-lon grid (rmu = the sines of its rows, no Gaussian weights, no PT panels: INV_TRANS(LDLATLON) only);
+  // shiftll: LDSHIFTLL, rows and longitudes offset by half a cell (the longitude half by g.llphase in k_prepack_inv)
+  bool ldll = false, shiftll = false;
   double ra = 6371229.0;
   // ---- global geometry (identical on every task)
   std::vector<int> nloen, nmen, ndglu, procm;  // procm[m]: owning task (0-based) of wavenumber m
@@ -1045,7 +1048,12 @@ static int setup_arguments(const emi_setup_t *cfg, const emi_legpol_io_t *io, Le
   if (!cfg) EMI_FAIL(EMI_ERR_ARG, "emi_setup: null config");
   if (cfg->kdgl <= 0 || cfg->kdgl % 2 != 0) EMI_FAIL(EMI_ERR_ARG, "SETUP_TRANS: KDGL IS NOT A POSITIVE, EVEN NUMBER");
   if (cfg->lduseflt) EMI_FAIL(EMI_ERR_UNSUPPORTED, "SETUP_TRANS: LDUSEFLT not supported (as gpu/external/setup_trans.F90:442)");
-  if (cfg->ldll) EMI_FAIL(EMI_ERR_UNSUPPORTED, "SETUP_TRANS: LDLL lat-lon grids not supported (as gpu/external/setup_trans.F90:309)");
+  if (cfg->ldshiftll && !cfg->ldll) EMI_FAIL(EMI_ERR_ARG, "SETUP_TRANS: LDSHIFTLL WITHOUT LDLL");
+  if (cfg->ldll) {  // one row length: KDLON, or a KLOEN whose entries are all equal
+    if (!cfg->kloen && cfg->kdlon <= 0) EMI_FAIL(EMI_ERR_ARG, "SETUP_TRANS: LDLL NEEDS KDLON (OR A UNIFORM KLOEN)");
+    for (int j = 1; cfg->kloen && j < cfg->kdgl; j++)
+      if (cfg->kloen[j] != cfg->kloen[0]) EMI_FAIL(EMI_ERR_ARG, "SETUP_TRANS: LDLL NEEDS ONE ROW LENGTH (KLOEN(%d) = %d, KLOEN(1) = %d)", j + 1, cfg->kloen[j], cfg->kloen[0]);
+  }
   if (cfg->ldstretch) EMI_FAIL(EMI_ERR_UNSUPPORTED, "SETUP_TRANS: PSTRET stretching not supported");
   if (cfg->precision != 0 && cfg->precision != 8 && cfg->precision != 4)
     EMI_FAIL(EMI_ERR_ARG, "emi_setup: precision must be 8 (fp64, the _dp library) or 4 (fp32, _sp), got %d", cfg->precision);
@@ -1055,6 +1063,7 @@ static int setup_arguments(const emi_setup_t *cfg, const emi_legpol_io_t *io, Le
     std::string mode(io->io);
     while (!mode.empty() && mode.back() == ' ') mode.pop_back();
     if (G.nproc_all > 1) EMI_FAIL(EMI_ERR_UNSUPPORTED, "SETUP_TRANS:CDIO_LEGPOL OPTIONS ONLY FOR NPROC=1 ");
+    if (cfg->ldll) EMI_FAIL(EMI_ERR_UNSUPPORTED, "SETUP_TRANS: CDIO_LEGPOL is not available with LDLL (the file format describes Gaussian latitudes)");
     if (mode == "readf" || mode == "READF")
       *lp_mode = LP_READF;
     else if (mode == "writef" || mode == "WRITEF")
@@ -1074,7 +1083,10 @@ static int setup_geometry(const emi_setup_t *cfg, Plan &P, std::vector<long long
   const int L = P.ndgl;
   int ndlon = cfg->kdlon > 0 ? cfg->kdlon : 2 * L;
   P.nloen.assign(L, ndlon);
-  if (cfg->kloen) {
+  if (P.ldll) {
+    if (cfg->kloen) P.nloen.assign(L, cfg->kloen[0]);  // uniform (setup_arguments); NDGL may be KDGL + 2
+    if (P.nloen[0] <= 0) EMI_FAIL(EMI_ERR_ARG, "SETUP_TRANS: KLOEN INVALID (ONE or MORE POINTS <= 0)");
+  } else if (cfg->kloen) {
     ndlon = 0;
     for (int j = 0; j < L; j++) {
       if (cfg->kloen[j] <= 0) EMI_FAIL(EMI_ERR_ARG, "SETUP_TRANS: KLOEN INVALID (ONE or MORE POINTS <= 0)");
@@ -1090,13 +1102,35 @@ static int setup_geometry(const emi_setup_t *cfg, Plan &P, std::vector<long long
   for (int j = 0; j < L; j++) cum[j + 1] = cum[j] + P.nloen[j];
   if (cum[L] > 2000000000LL) EMI_FAIL(EMI_ERR_UNSUPPORTED, "grid too large for 32-bit point offsets");
   P.ngptotg = (int)cum[L];
-  emi::gauss_latitudes(L, P.rmu, P.rw);
   P.cos2.assign(L, 0.0);
   P.racthe.assign(L, 0.0);
-  for (int j = 0; j < L; j++) {
-    double th = std::asin(P.rmu[j]), c = std::cos(th);
-    P.cos2[j] = c * c;
-    P.racthe[j] = 1.0 / c / P.ra;
+  if (P.ldll) {
+    // The rows of the lat-lon grid (setup_trans.F90:258-271), north to south, row L-1-j the mirror of row j.  Unshifted: colatitude
+    // j pi / (L - 2), j = 0 .. L/2 - 1 -- the pole (mu = 1) down to the equator (mu = 0, held twice); shifted: (j + 1/2) pi / L.
+    // mu = cos(colatitude) exactly on the row (the reference moves the pole and equator rows, suleg_mod.F90:314-332).
+    const double pi = 2.0 * std::asin(1.0), eps = 1000.0 * 2.220446049250313e-16;
+    P.rmu.assign(L, 0.0);
+    P.rw.assign(L, 0.0);  // no Gaussian weights
+    for (int j = 0; j < L / 2; j++) {
+      const double th = P.shiftll ? ((double)j + 0.5) * pi / (double)L : (double)j * pi / (double)(L - 2);
+      double mu = std::cos(th), c = std::sin(th);
+      if (!P.shiftll && j == 0) mu = 1.0, c = 0.0;
+      if (!P.shiftll && j == L / 2 - 1) mu = 0.0, c = 1.0;
+      // 1 / (a cos(latitude)); on a pole row the reference's regularised 1 / ((cos + eps) a) (suleg_mod.F90:179,352), which keeps u, v and
+      // the derivatives finite there.  Off the poles eps would cost eps / cos -- 2.5e-11 on the row next to the pole of a 0.5 degree grid,
+      // more than the parity bounds of this library -- so it is left out where it is not needed.
+      const double ract = c > 0.0 ? 1.0 / c / P.ra : 1.0 / eps / P.ra;
+      P.rmu[j] = mu, P.rmu[L - 1 - j] = -mu;
+      P.cos2[j] = P.cos2[L - 1 - j] = c * c;
+      P.racthe[j] = P.racthe[L - 1 - j] = ract;
+    }
+  } else {
+    emi::gauss_latitudes(L, P.rmu, P.rw);
+    for (int j = 0; j < L; j++) {
+      double th = std::asin(P.rmu[j]), c = std::cos(th);
+      P.cos2[j] = c * c;
+      P.racthe[j] = 1.0 / c / P.ra;
+    }
   }
   emi::wavenumber_cutoffs(P.nsmax, L, P.nloen, P.reduced, P.cos2, P.nmen, P.ndglu);
   return 0;
@@ -1211,7 +1245,7 @@ static void setup_local_tables(Plan &P, const std::vector<long long> &cum, Setup
   }
   P.nspec2 = ipos;
   P.p_elems = poff;
-  P.pt_elems = ptoff;
+  P.pt_elems = P.ldll ? 0 : ptoff;  // LDLL: no direct transform, no transposed panels
   P.wrows_total = P.wbase[NU];
   T.rowm.resize(P.wrows_total);
   for (int ml = 0; ml < NU; ml++)
@@ -1353,7 +1387,7 @@ static void panel_by_recurrence(const Plan &P, int ml, std::vector<double> &pan)
   for (int j = 0; j < nd; j++) {
     double mu = P.rmu[isl0 + j];
     for (int par = 0; par < 2; par++) {
-      emi::legendre_column(lc, mu, par, col.data(), corr.data());
+      emi::legendre_column(lc, mu, par, col.data(), corr.data(), P.ldll);
       double *dst = pan.data() + (size_t)par * nk * ld;
       for (int k = 0; m + 2 * k + par <= N + 1; k++) dst[(size_t)k * ld + j] = col[m + 2 * k + par];
     }
@@ -1364,11 +1398,11 @@ static void panel_by_recurrence(const Plan &P, int ml, std::vector<double> &pan)
 // recurrence (EMI_LEGPOL_HOST=1; the host and the device recurrence agree bit for bit, tests/test_gpu_parity.py).
 static int setup_panels_host(Plan &P, const LegpolSource *src, bool belousov, bool all_m) {
   const size_t esz = P.esz;
-  if (P.dev_allocs.alloc((void **)&P.d_P, (size_t)P.p_elems * esz) || P.dev_allocs.alloc((void **)&P.d_PT, (size_t)P.pt_elems * esz))
+  if (P.dev_allocs.alloc((void **)&P.d_P, (size_t)P.p_elems * esz) || (P.pt_elems && P.dev_allocs.alloc((void **)&P.d_PT, (size_t)P.pt_elems * esz)))
     EMI_FAIL(EMI_ERR_RUNTIME, "cannot allocate %.2f GiB for the Legendre panels", (P.p_elems + P.pt_elems) * (double)esz / (1 << 30));
   std::vector<std::vector<double>> belpan;
   if (belousov) panels_belousov(P, belpan);
-  if (emi_dev_memset(P.d_P, 0, (size_t)P.p_elems * esz, 0) || emi_dev_memset(P.d_PT, 0, (size_t)P.pt_elems * esz, 0)) return EMI_ERR_RUNTIME;
+  if (emi_dev_memset(P.d_P, 0, (size_t)P.p_elems * esz, 0) || (P.d_PT && emi_dev_memset(P.d_PT, 0, (size_t)P.pt_elems * esz, 0))) return EMI_ERR_RUNTIME;
   emi_stream_sync(0);
   std::atomic<int> bad{0};
   emi::parallel_for(P.nump, [&](int ml) {
@@ -1381,6 +1415,10 @@ static int setup_panels_host(Plan &P, const LegpolSource *src, bool belousov, bo
       panel_from_source(P, *src, ml, pan);
     else
       panel_by_recurrence(P, ml, pan);
+    // unshifted LDLL: the odd functions vanish on the equator row; Belousov's series leaves rounding there (cos(k acos(0)) is not 0
+    // for odd k), which would make the two copies of the equator differ in their last bits
+    if (P.ldll && !P.shiftll && nd == P.ndgnh)
+      for (int k = 0; k < nk; k++) pan[((size_t)nk + k) * ld + (nd - 1)] = 0.0;
     // the recurrences always run in double (as the reference's _sp build does: the JPRD work arrays of suleg_mod.F90:130-162);
     // the fp32 library rounds the finished panel once
     std::vector<float> cvt;
@@ -1393,6 +1431,10 @@ static int setup_panels_host(Plan &P, const LegpolSource *src, bool belousov, bo
       return rc;
     };
     if (put(P.d_P + P.offS[ml] * esz, pan)) bad = 1;
+    if (!P.d_PT) {
+      emi_stream_sync(0);
+      return;
+    }
     const int ldk = P.ldk[ml], ndp = roundup(std::max(nd, 1), 16);  // = the panel extent behind offTA (pant)
     std::vector<double> pt((size_t)2 * ndp * ldk, 0.0);
     for (int par = 0; par < 2; par++)
@@ -1423,6 +1465,19 @@ static int setup_device_tables(Plan &P, const SetupTables &T) {
       upload(P.dev_allocs, P.offTS, &g.offTS) || upload(P.dev_allocs, P.offTA, &g.offTA))
     return EMI_ERR_RUNTIME;
   if (!T.rowtable) g.fftrow = nullptr;  // one task: rows are fbase[lat] + m, no table (the upload stays the plan's)
+  g.llphase = nullptr;
+  if (P.shiftll) {
+    // LDSHIFTLL: longitudes (i + 1/2) 2 pi / nlon = a rotation of the Fourier coefficient of wavenumber m by e^{i m pi / nlon}
+    // (fsc_mod.F90:86-127 does it per row); one row length, so one factor per wavenumber, applied by k_prepack_inv
+    const double pi = 2.0 * std::asin(1.0);
+    std::vector<double> ph(2 * (size_t)std::max(P.nump, 1), 0.0);
+    for (int ml = 0; ml < P.nump; ml++) {
+      const double a = (double)P.mval[ml] * pi / (double)P.nloen[0];
+      ph[2 * ml] = P.mval[ml] == 0 ? 1.0 : std::cos(a);
+      ph[2 * ml + 1] = P.mval[ml] == 0 ? 0.0 : std::sin(a);
+    }
+    if (upload(P.dev_allocs, ph, &g.llphase)) return EMI_ERR_RUNTIME;
+  }
   return 0;
 }
 
@@ -1452,6 +1507,7 @@ static int setup_panels_device(Plan &P) {
   LegPolDev la{};
   la.ndgnh = P.ndgnh;
   la.nmax = nmax;
+  la.nofloor = P.ldll ? 1 : 0;
   if (upload(tmp, dcl, &la.dcl) || upload(tmp, ddl, &la.ddl) || upload(tmp, zf, &la.zfac) || upload(tmp, mu, &la.mu) || upload(tmp, blk, &la.blk)) return EMI_ERR_RUNTIME;
   EmiRange rg_suleg(EMI_LBL_SULEG);  // GSTATS 140
   EMI_LAUNCH_P(P.esz, k_legpol, blk.size() / 2, 64, 0, (emi_stream_t)0, P.g, la);
@@ -1477,7 +1533,9 @@ extern "C" int emi_setup_legpol(const emi_setup_t *cfg, const emi_legpol_io_t *i
   std::unique_ptr<Plan> pp(new Plan());  // whatever exit is taken from here on, the plan frees what it has allocated
   Plan &P = *pp;
   P.nsmax = cfg->ksmax;
-  P.ndgl = cfg->kdgl;
+  P.ldll = cfg->ldll != 0;
+  P.shiftll = P.ldll && cfg->ldshiftll != 0;
+  P.ndgl = cfg->kdgl + (P.ldll && !P.shiftll ? 2 : 0);  // unshifted LDLL: both poles, and the equator twice (setup_trans.F90:258-271)
   P.ndgnh = (P.ndgl + 1) / 2;
   P.ra = G.ra;
   P.esz = cfg->precision == 4 ? 4 : 8;
@@ -1600,6 +1658,10 @@ extern "C" int emi_inq_int(int kresol, const char *name, int *value) {
     *value = P->ndgl;
   else if (s == "nsmax")
     *value = P->nsmax;
+  else if (s == "ldll")
+    *value = P->ldll ? 1 : 0;
+  else if (s == "lshiftll" || s == "ldshiftll")
+    *value = P->shiftll ? 1 : 0;
   else if (s == "ndlon")
     *value = *std::max_element(P->nloen.begin(), P->nloen.end());
   else if (s == "nproc")
@@ -1669,8 +1731,10 @@ extern "C" int emi_inq_real_array(int kresol, const char *name, double *out, int
   const std::vector<double> *v = nullptr;
   if (s == "rmu" || s == "pmu")
     v = &P->rmu;
-  else if (s == "rgw" || s == "pgw" || s == "rw")
+  else if (s == "rgw" || s == "pgw" || s == "rw") {
+    if (P->ldll) EMI_FAIL(EMI_ERR_UNSUPPORTED, "TRANS_INQ: %s: a handle set up with LDLL keeps no Gaussian weights", s.c_str());
     v = &P->rw;
+  }
   else if (s == "racthe")
     v = &P->racthe;
   else if (s == "rlapin" || s == "plapin") {
@@ -2354,14 +2418,16 @@ struct Call {
   void *gp, *gpuv, *gp3a, *gp3b, *gp2;
   int gp_nfld;
   int ldscders, ldvorgp, lddivgp, lduvder;  // LDSCDERS, LDVORGP, LDDIVGP, LDUVDER: 0 from an emi_dirtrans_t
+  int ldlatlon;                             // LDLATLON: 0 from an emi_dirtrans_t
 };
 template <class A>
 static Call to_call(const A &a) {
   Call c{a.mem_space, (emi_stream_t)a.stream, a.ext, a.vsets, a.kproma,
          (void *)a.spvor, (void *)a.spdiv, (void *)a.spscalar, (void *)a.spsc3a, (void *)a.spsc3b, (void *)a.spsc2,
          a.nf_uv, a.nf_scalar, a.sc3a_nlev, a.sc3a_nvar, a.sc3b_nlev, a.sc3b_nvar, a.nf_sc2,
-         (void *)a.gp, (void *)a.gpuv, (void *)a.gp3a, (void *)a.gp3b, (void *)a.gp2, a.gp_nfld, 0, 0, 0, 0};
-  if constexpr (std::is_same<A, emi_invtrans_t>::value) c.ldscders = a.ldscders, c.ldvorgp = a.ldvorgp, c.lddivgp = a.lddivgp, c.lduvder = a.lduvder;
+         (void *)a.gp, (void *)a.gpuv, (void *)a.gp3a, (void *)a.gp3b, (void *)a.gp2, a.gp_nfld, 0, 0, 0, 0, 0};
+  if constexpr (std::is_same<A, emi_invtrans_t>::value)
+    c.ldscders = a.ldscders, c.ldvorgp = a.ldvorgp, c.lddivgp = a.lddivgp, c.lduvder = a.lduvder, c.ldlatlon = a.ldlatlon;
   return c;
 }
 
@@ -2978,6 +3044,7 @@ extern "C" int emi_gpnorm(int kresol, int mem_space, const void *gp, int gp_nfld
   Plan *Pp = get_plan(kresol);
   if (!Pp) EMI_FAIL(EMI_ERR_STATE, "GPNORM_TRANS: unknown resolution %d", kresol);
   Plan &P = *Pp;
+  if (P.ldll) EMI_FAIL(EMI_ERR_UNSUPPORTED, "GPNORM_TRANS: not available on a handle set up with LDLL (it keeps no Gaussian weights)");
   if (kfields <= 0 || !gp || !ave || !pmin || !pmax) EMI_FAIL(EMI_ERR_ARG, "GPNORM_TRANS: bad arguments");
   if (gp_nfld < kfields) EMI_FAIL(EMI_ERR_ARG, "GPNORM_TRANS_CTL:SECOND DIMENSION OF PGP TOO SMALL (%d < %d)", gp_nfld, kfields);
   if (G.nproc_all > 1 && !G.hc_gather) EMI_FAIL(EMI_ERR_STATE, "GPNORM_TRANS: several tasks and no host collectives (emi_set_host_collectives)");
@@ -3647,6 +3714,13 @@ static int transform(int kresol, const Call &c, bool inverse, bool adj) {
   const char *who = inverse ? (adj ? "DIR_TRANSAD" : "INV_TRANS") : (adj ? "INV_TRANSAD" : "DIR_TRANS");
   Plan *Pp = get_plan(kresol);
   if (!Pp) EMI_FAIL(EMI_ERR_STATE, "%s: unknown resolution %d", who, kresol);
+  // A handle set up with LDLL holds the inverse panels of its lat-lon rows and nothing else: no Gaussian grid beside them (the
+  // reference keeps both on one handle), no Gaussian weights, no panels of the direct transform
+  if (Pp->ldll && !(inverse && !adj))
+    EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: not available on a handle set up with LDLL (it serves INV_TRANS with LDLATLON only)", who);
+  if (Pp->ldll && !c.ldlatlon)
+    EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: a handle set up with LDLL holds no Gaussian grid: call it with LDLATLON=.TRUE.", who);
+  if (!Pp->ldll && c.ldlatlon) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: LDLATLON needs a handle set up with LDLL", who);
   return G.nprtrv > 1 ? vset_transform(*Pp, c, inverse, adj, who) : wset_transform(*Pp, c, inverse, adj, who);
 }
 extern "C" int emi_inv_trans(int kresol, const emi_invtrans_t *args) {

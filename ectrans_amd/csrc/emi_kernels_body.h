@@ -115,6 +115,10 @@ EMI_KERNEL_LB(256) void k_prepack_inv(EmiGeomDev g, const SpecSrc *flds, int nfl
             if (m == 0) out.y = 0.0;
           }
         }
+        if (g.llphase != nullptr) {  // LDSHIFTLL: longitudes (i + 1/2) 2 pi / nlon, out *= e^{i m pi / nlon} (m = 0: factor 1, out.y stays 0)
+          const real_t pc = (real_t)g.llphase[2 * ml], ps = (real_t)g.llphase[2 * ml + 1];
+          out = mk2(out.x * pc - out.y * ps, out.x * ps + out.y * pc);
+        }
       }
     }
     *(real2 *)(W + row * ldw + 2 * f) = out;
@@ -3068,11 +3072,14 @@ EMI_KERNEL_LB(256) void k_gridcopy(const GridFld *src, const GridFld *dst, int n
 // taken (only that step and earlier ones can rescale it, supolf_mod.F90:222-236), so the two values in
 // flight live in registers and nothing is revisited.  (m = 0, 1 use the ordinary recurrence on the host.)
 // ==========================================================================================
-EMI_DEVFN double legpol_final(double v, int corr) {
+// nofloor (LDLL handles): the rescaling is undone without the reference's floor, which puts 2.2e-16 where the function is 1e-110 (and
+// where it is negative).  A reduced Gaussian grid never reads those entries (NMEN cuts them off); the rows of a lat-lon grid read every
+// m, and u, v multiply them by 1 / cos(lat).  Without it the values underflow to what they are, and P_n^m(+-1) = 0 exactly.
+EMI_DEVFN double legpol_final(double v, int corr, bool nofloor) {
   const double big = 1.0e+100, eps = 2.220446049250313e-16;
   for (int j = 1; j <= corr; j++) {
     v /= big;
-    if (v < eps) v = eps;  // sic: no ABS in the reference (supolf_mod.F90:241-243)
+    if (!nofloor && v < eps) v = eps;  // sic: no ABS in the reference (supolf_mod.F90:241-243)
   }
   return v;
 }
@@ -3087,6 +3094,7 @@ EMI_KERNEL_LB(64) void k_legpol(EmiGeomDev g, LegPolDev a) {
   const int ld = g.ldp[ml], ldk = g.ldk[ml];
   real_t *Pp = (real_t *)g.P + (par ? g.offA[ml] : g.offS[ml]) + j;                      // + k * ld
   real_t *PTp = (real_t *)g.PT + (par ? g.offTA[ml] : g.offTS[ml]) + (long long)j * ldk;  // + k
+  const bool pt = g.PT != nullptr;  // an LDLL handle has no transposed panels
   const double *dcl = a.dcl + (long long)ml * (nmax + 1), *ddl = a.ddl + (long long)ml * (nmax + 1);
   const double eps = 2.220446049250313e-16, big = 1.0e+100, small = 1.0e-100;
   double x = a.mu[a.ndgnh - nd + j];
@@ -3130,9 +3138,9 @@ EMI_KERNEL_LB(64) void k_legpol(EmiGeomDev g, LegPolDev a) {
     }
     const double nw = ((x * x - ddl[n - 2]) * w1 - dcl[n - 4] * w0) / dcl[n - 2];
     if (kout < nk) {
-      const double v = legpol_final(w0, corr3 - ev);
+      const double v = legpol_final(w0, corr3 - ev, a.nofloor != 0);
       Pp[(long long)kout * ld] = (real_t)v;
-      PTp[kout] = (real_t)v;
+      if (pt) PTp[kout] = (real_t)v;
     }
     kout++;
     w0 = w1;
@@ -3140,15 +3148,15 @@ EMI_KERNEL_LB(64) void k_legpol(EmiGeomDev g, LegPolDev a) {
   }
   // the last two values (or the starting values when no step was taken)
   if (kout < nk) {
-    const double v = legpol_final(w0, corr3 - ev);
+    const double v = legpol_final(w0, corr3 - ev, a.nofloor != 0);
     Pp[(long long)kout * ld] = (real_t)v;
-    PTp[kout] = (real_t)v;
+    if (pt) PTp[kout] = (real_t)v;
   }
   kout++;
   if (kout < nk && m + par + 2 <= nmax) {
-    const double v = legpol_final(w1, corr3 - ev);
+    const double v = legpol_final(w1, corr3 - ev, a.nofloor != 0);
     Pp[(long long)kout * ld] = (real_t)v;
-    PTp[kout] = (real_t)v;
+    if (pt) PTp[kout] = (real_t)v;
   }
 }
 

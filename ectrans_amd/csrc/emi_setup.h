@@ -147,7 +147,8 @@ inline LegCoef legendre_coefficients(int m, int nmax) {
 }
 
 // out[n] for n = 0..nmax (only the entries of parity `par` relative to m are defined for m>=2)
-inline void legendre_column(const LegCoef &c, double mu_in, int par, double *out, int *corr /* [nmax+1] scratch */) {
+// nofloor (lat-lon rows, which read every m at every latitude): the rescaling is undone without the reference's floor
+inline void legendre_column(const LegCoef &c, double mu_in, int par, double *out, int *corr /* [nmax+1] scratch */, bool nofloor = false) {
   const int m = c.m, nmax = c.nmax;
   const double eps = 2.220446049250313e-16;
   double x = mu_in;
@@ -220,7 +221,7 @@ inline void legendre_column(const LegCoef &c, double mu_in, int par, double *out
   for (int n = m + par; n <= nmax; n += 2)
     for (int j = 1; j <= corr[n]; j++) {
       out[n] /= big;
-      if (out[n] < eps) out[n] = eps;  // sic: the reference has no ABS here (supolf_mod.F90:241-243)
+      if (!nofloor && out[n] < eps) out[n] = eps;  // sic: the reference has no ABS here (supolf_mod.F90:241-243)
     }
 }
 

@@ -36,6 +36,7 @@ struct EmiGeomDev {
   const int *lattile_pref;     // [nump+1] prefix of ceil(ndglu/64)
   const int *ktile_pref;       // [nump+1] k_leg_dir's row tiles: 2 floor(nk/128) one-parity tiles + 0 | 1 | 2 for the rest (nk = wrows/2)
   const double *specw;         // [nspec2 local] SPECNORM weight of every spectral entry (0, 1 or 2)
+  const double *llphase;       // LDSHIFTLL: [nump][2] (cos, sin) of m pi / nlon, the half-cell longitude shift; NULL on every other handle
 };
 
 // k_vd2uv (VORDIV_TO_UV): spectral tables of one task, no resolution handle
@@ -55,6 +56,7 @@ struct LegPolDev {  // SETUP_TRANS on the device: inputs of k_legpol
   const double *zfac;      // [nump] sqrt(2m-1) prod_{j<m} sqrt((2j-1)/(2j))
   const int *blk;          // [nblocks][2]: local wavenumber, parity << 16 | latitude tile (64 latitudes)
   int ndgnh, nmax;
+  int nofloor;             // LDLL: no "v < eps -> eps" floor when the 1e+-100 rescaling is undone (legpol_final)
 };
 
 enum { SPK_COPY = 0, SPK_U = 1, SPK_V = 2, SPK_NSD = 3, SPK_U_AD = 4, SPK_V_AD = 5 };  // *_AD: adjoint of UVTVD (DIR_TRANSAD)

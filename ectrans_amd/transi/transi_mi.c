@@ -5,6 +5,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <hip/hip_runtime_api.h> /* device copies of a lat-lon rgp with lglobal (trans_invtrans) */
+
 #include "../../include/ectrans_mi.h"
 
 static int g_limit = 100, g_limit_set = 0;
@@ -103,6 +105,18 @@ int trans_set_resol(struct Trans_t *t, int ndgl, const int *nloen) {
   return TRANS_SUCCESS;
 }
 
+/* transi.c:94-114: nlat even = the shifted grid (no poles, no equator); nlat odd = poles and equator, set up with ndgl = nlat - 1
+ * (SETUP_TRANS works with ndgl + 2 rows, the equator twice) */
+int trans_set_resol_lonlat(struct Trans_t *t, int nlon, int nlat) {
+  if (nlon <= 0 || nlat < 2) return TRANS_ERROR;
+  free(t->nloen);
+  t->nloen = NULL;
+  t->nlon = nlon;
+  t->ndgl = nlat % 2 == 0 ? nlat : nlat - 1;
+  t->llatlon = nlat % 2 == 0 ? 2 : 1;
+  return TRANS_SUCCESS;
+}
+
 int trans_set_trunc(struct Trans_t *t, int nsmax) {
   t->nsmax = nsmax;
   return TRANS_SUCCESS;
@@ -132,7 +146,8 @@ int trans_setup(struct Trans_t *t) {
   int rc = trans_init();
   if (rc) return rc;
   if (t->ndgl <= 0 || (!t->nloen && t->nlon <= 0)) return TRANS_MISSING_ARG;
-  if (t->llatlon || t->flt > 0) return TRANS_NOTIMPL;
+  if (t->flt > 0) return TRANS_NOTIMPL;
+  if (t->llatlon && (t->nlon <= 0 || t->readfp || t->writefp || t->cachesize > 0)) return TRANS_NOTIMPL; /* no Legendre file of lat-lon rows */
   if (t->nsmax < 0) t->nsmax = t->ndgl - 1; /* default: linear truncation on the given latitudes */
   emi_setup_t cfg;
   memset(&cfg, 0, sizeof(cfg));
@@ -141,6 +156,8 @@ int trans_setup(struct Trans_t *t) {
   cfg.kloen = t->nloen;
   cfg.kdlon = t->nlon;
   cfg.precision = 8;
+  cfg.ldll = t->llatlon != 0;
+  cfg.ldshiftll = t->llatlon == 2;
   emi_legpol_io_t io;
   memset(&io, 0, sizeof(io));
   if (t->cachesize > 0 && !t->cache) { /* transi_module.F90:737-741 */
@@ -169,6 +186,7 @@ int trans_setup(struct Trans_t *t) {
   emi_inq_int(t->handle, "ngptot", &t->ngptot);
   emi_inq_int(t->handle, "ngptotg", &t->ngptotg);
   emi_inq_int(t->handle, "ngptotmx", &t->ngptotmx);
+  if (t->llatlon == 1) t->ngptotg -= t->nlon; /* the user's global field has nlat rows: the equator once (transi_module.F90:1140) */
   return TRANS_SUCCESS;
 }
 
@@ -176,15 +194,17 @@ static int inq_one(struct Trans_t *t, const char *v) {
   const int ns = t->nsmax + 1;
   if (!strcmp(v, "rmu") || !strcmp(v, "rgw")) {
     double **dst = !strcmp(v, "rmu") ? &t->rmu : &t->rgw;
-    if (!*dst) *dst = (double *)malloc(sizeof(double) * (size_t)t->ndgl);
-    return emi_inq_real_array(t->handle, v, *dst, t->ndgl) ? TRANS_ERROR : TRANS_SUCCESS;
+    const int nrows = t->llatlon == 1 ? t->ndgl + 2 : t->ndgl; /* the rows of the handle (a lat-lon one has no rgw: the library refuses) */
+    if (!*dst) *dst = (double *)malloc(sizeof(double) * (size_t)nrows);
+    return emi_inq_real_array(t->handle, v, *dst, nrows) ? TRANS_ERROR : TRANS_SUCCESS;
   }
   struct {
     const char *name, *emi;
     int **dst;
     int len;
   } ints[] = {{"nasm0", "nasm0", &t->nasm0, ns}, {"nmyms", "myms", &t->nmyms, ns}, {"ndglu", "ndglu", &t->ndglu, ns},
-              {"nnmeng", "nmen", &t->nnmeng, t->ndgl}, {"nmeng", "nmen", &t->nnmeng, t->ndgl}};
+              {"nnmeng", "nmen", &t->nnmeng, t->llatlon == 1 ? t->ndgl + 2 : t->ndgl},
+              {"nmeng", "nmen", &t->nnmeng, t->llatlon == 1 ? t->ndgl + 2 : t->ndgl}};
   for (size_t i = 0; i < sizeof(ints) / sizeof(ints[0]); i++)
     if (!strcmp(v, ints[i].name)) {
       if (!*ints[i].dst) *ints[i].dst = (int *)malloc(sizeof(int) * (size_t)ints[i].len);
@@ -232,6 +252,13 @@ static int run_and_wait(int rc, int handle) {
   return emi_wait(handle) ? TRANS_ERROR : TRANS_SUCCESS;
 }
 
+/* a handle set up with trans_set_resol_lonlat serves trans_invtrans only (the library keeps no Gaussian grid beside the lat-lon one) */
+static int lonlat_refused(const struct Trans_t *t, const char *who) {
+  if (!t->llatlon) return 0;
+  fprintf(stderr, "%s: ERROR: not available on a lonlat handle (LDLL): it serves trans_invtrans only\n", who);
+  return 1;
+}
+
 struct DirTrans_t new_dirtrans(struct Trans_t *t) {
   struct DirTrans_t d;
   memset(&d, 0, sizeof(d));
@@ -245,6 +272,7 @@ int trans_dirtrans(struct DirTrans_t *d) {
   if (d->nscalar > 0 && !d->rspscalar) return TRANS_MISSING_ARG;
   if (d->nvordiv > 0 && (!d->rspvor || !d->rspdiv)) return TRANS_MISSING_ARG;
   if (d->rmeanu || d->rmeanv) return TRANS_NOTIMPL; /* LAM only */
+  if (lonlat_refused(d->trans, "trans_dirtrans")) return TRANS_NOTIMPL;
   emi_dirtrans_t a;
   memset(&a, 0, sizeof(a));
   a.mem_space = EMI_MEM_AUTO; /* rgp / rsp* in device memory are used in place, host arrays are staged (emi_ptr_space) */
@@ -273,6 +301,40 @@ struct InvTrans_t new_invtrans(struct Trans_t *t) {
   return v;
 }
 
+/* llatlon == 1 with lglobal: rgp is [nfld][ngptotg] = nlat rows per field, the library computes NDGL = nlat + 1 rows (the equator
+ * twice, rows NDGL/2 and NDGL/2 + 1).  The transform runs into a scratch array in the memory rgp lives in and every field is
+ * copied across without the second equator row (transi_module.F90:1577-1597) -- device to device when rgp is in device memory. */
+static int invtrans_lonlat_global(struct InvTrans_t *v, emi_invtrans_t *a) {
+  const struct Trans_t *t = v->trans;
+  const size_t nlon = (size_t)t->nlon, ng = (size_t)t->ngptot, ngg = (size_t)t->ngptotg, nf = (size_t)a->gp_nfld;
+  const size_t north = (size_t)(t->ndgl + 2) / 2 * nlon, south = ngg - north; /* points up to and including the equator; the rest */
+  const int dev = emi_ptr_space(v->rgp) == EMI_MEM_DEVICE;
+  double *tmp = NULL;
+  if (dev) {
+    if (hipMalloc((void **)&tmp, sizeof(double) * ng * nf) != hipSuccess) return TRANS_ERROR;
+  } else if (!(tmp = (double *)malloc(sizeof(double) * ng * nf))) {
+    return TRANS_ERROR;
+  }
+  a->gp = tmp;
+  int rc = run_and_wait(emi_inv_trans(t->handle, a), t->handle);
+  if (!rc && dev) {
+    if (hipMemcpy2D(v->rgp, ngg * 8, tmp, ng * 8, north * 8, nf, hipMemcpyDeviceToDevice) != hipSuccess ||
+        hipMemcpy2D(v->rgp + north, ngg * 8, tmp + north + nlon, ng * 8, south * 8, nf, hipMemcpyDeviceToDevice) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess)
+      rc = TRANS_ERROR;
+  } else if (!rc) {
+    for (size_t f = 0; f < nf; f++) {
+      memcpy(v->rgp + f * ngg, tmp + f * ng, north * 8);
+      memcpy(v->rgp + f * ngg + north, tmp + f * ng + north + nlon, south * 8);
+    }
+  }
+  if (dev)
+    (void)hipFree(tmp);
+  else
+    free(tmp);
+  return rc;
+}
+
 int trans_invtrans(struct InvTrans_t *v) {
   if (v->count++ > 0) return TRANS_STALE_ARG;
   if (!v->trans || !v->rgp) return TRANS_MISSING_ARG;
@@ -299,6 +361,8 @@ int trans_invtrans(struct InvTrans_t *v) {
   a.gp = v->rgp;
   a.gp_nfld = 2 * v->nvordiv + v->nscalar + (v->lscalarders ? 2 * v->nscalar : 0) + (v->lvordivgp ? 2 * v->nvordiv : 0) +
               (v->luvder_EW ? 2 * v->nvordiv : 0);
+  a.ldlatlon = v->trans->llatlon != 0;
+  if (v->trans->llatlon == 1 && v->lglobal) return invtrans_lonlat_global(v, &a);
   return run_and_wait(emi_inv_trans(v->trans->handle, &a), v->trans->handle);
 }
 
@@ -315,6 +379,7 @@ int trans_dirtrans_adj(struct DirTransAdj_t *d) {
   if (d->nscalar > 0 && !d->rspscalar) return TRANS_MISSING_ARG;
   if (d->nvordiv > 0 && (!d->rspvor || !d->rspdiv)) return TRANS_MISSING_ARG;
   if (d->rmeanu || d->rmeanv) return TRANS_NOTIMPL;
+  if (lonlat_refused(d->trans, "trans_dirtrans_adj")) return TRANS_NOTIMPL;
   emi_dirtrans_t a;
   memset(&a, 0, sizeof(a));
   a.mem_space = EMI_MEM_AUTO; /* rgp / rsp* in device memory are used in place, host arrays are staged (emi_ptr_space) */
@@ -338,6 +403,7 @@ int trans_invtrans_adj(struct InvTransAdj_t *v) {
   if (v->nscalar > 0 && !v->rspscalar) return TRANS_MISSING_ARG;
   if (v->nvordiv > 0 && (!v->rspvor || !v->rspdiv)) return TRANS_MISSING_ARG;
   if (v->rmeanu || v->rmeanv) return TRANS_NOTIMPL;
+  if (lonlat_refused(v->trans, "trans_invtrans_adj")) return TRANS_NOTIMPL;
   if (check_global(v->trans, v->lglobal)) return TRANS_ERROR;
   emi_invtrans_t a;
   memset(&a, 0, sizeof(a));

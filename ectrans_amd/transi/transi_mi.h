@@ -6,9 +6,16 @@
  * (rgp[ngpblks][nfld][nproma], rsp[nspec2][nfld], transi.h:908-921), same return convention
  * (TRANS_SUCCESS = 0, negative error codes, trans_error_msg()).
  *
- * Not provided (outside SURVEY.md section 8): vordiv_to_UV,
- * LAM, lonlat, rmeanu/rmeanv (lglobal is honoured: one task, global == local).  They return
- * TRANS_NOTIMPL instead of being silently ignored.
+ * Not provided (outside SURVEY.md section 8): LAM, rmeanu/rmeanv (lglobal is honoured: one task, global == local).
+ * They return TRANS_NOTIMPL instead of being silently ignored.
+ *
+ * Regular lat-lon grids (trans_set_resol_lonlat, transi.h:186): trans_invtrans only.  The series is evaluated exactly on the
+ * grid's rows (the reference interpolates from a Gaussian grid, and its GPU build refuses lonlat).  nlat odd: poles and
+ * equator included, llatlon = 1; internally the equator is held twice, so ngptot = ngptotg + nlon: an rgp without lglobal
+ * has ngptot points per field (nlat + 1 rows), an rgp with lglobal has ngptotg = nlat * nlon and comes back without the
+ * duplicate row (host or device memory).  nlat even: the grid shifted by half a cell in both directions, llatlon = 2.
+ * trans_dirtrans and both adjoints return TRANS_NOTIMPL on such a handle; u, v and the derivatives are finite and
+ * meaningless on the two pole rows.
  */
 #ifndef TRANSI_MI_H
 #define TRANSI_MI_H
@@ -33,7 +40,7 @@ struct Trans_t {
   int nlon;   /* points per latitude of a regular grid (when nloen == NULL) */
   int nsmax;  /* spectral truncation */
   _bool lsplit;
-  int llatlon; /* must stay 0 */
+  int llatlon; /* 0: Gaussian grid; 1 / 2: lat-lon grid with / without poles and equator (trans_set_resol_lonlat) */
   int flt;     /* <= 0: Fast Legendre Transform not requested (the only supported setting) */
   /* Legendre polynomials from / to a file or a memory image (transi.h:719-722; set with trans_set_read,
    * trans_set_write, trans_set_cache; precedence read > write > cache as transi_module.F90:762-866) */
@@ -125,6 +132,7 @@ int trans_set_radius(double);      /* default 6371.22e3 (transi's own default) *
 int trans_init(void);
 int trans_new(struct Trans_t *);
 int trans_set_resol(struct Trans_t *, int ndgl, const int *nloen);
+int trans_set_resol_lonlat(struct Trans_t *, int nlon, int nlat);   /* transi.h:186 */
 int trans_set_trunc(struct Trans_t *, int nsmax);
 int trans_set_read(struct Trans_t *, const char *filepath);          /* transi.h:192 */
 int trans_set_write(struct Trans_t *, const char *filepath);         /* transi.h:193 */

@@ -81,12 +81,22 @@ typedef struct {
   int precision;     /* bytes per real of every data array of this resolution: 8 (or 0) =
                       * fp64, the reference's libtrans_dp (JPRB=JPRD); 4 = fp32, its
                       * libtrans_sp (JPRB=JPRM).  Setup arithmetic is double in both.       */
-  /* options the reference GPU backend also refuses (gpu/external/setup_trans.F90:309,442):
-   * a non-zero value returns EMI_ERR_UNSUPPORTED */
+  /* lduseflt, ldstretch: options the reference GPU backend also refuses (gpu/external/setup_trans.F90:442): a non-zero
+   * value returns EMI_ERR_UNSUPPORTED.  ldll: LDLL, a regular latitude-longitude grid (see ldshiftll below). */
   int lduseflt, ldll, ldstretch;
   int lduserpnm;     /* LDUSERPNM: 1 = Belousov's generator for the Legendre polynomials (supol_mod.F90; the
                       * default of the Fortran API), 0 = the per-wavenumber recurrence SUPOLF (what the
                       * benchmark and transi pass; computed on the device).  The two agree to ~1e-12.       */
+  int ldshiftll;     /* LDSHIFTLL (with ldll).  ldll sets up a regular lat-lon grid for INV_TRANS(LDLATLON) (setup_trans.F90:258-271):
+                      * one row length (kdlon, or a kloen of equal entries), NMEN = min(KSMAX, (nlon-1)/2) on every row.
+                      *   ldshiftll == 0: kdgl = nlat - 1 (nlat odd); NDGL = kdgl + 2 rows at 90 - (j-1) 180/(nlat-1) degrees,
+                      *     j = 1 .. NDGL/2, mirrored in the south: both poles, and the equator held twice (rows NDGL/2 and
+                      *     NDGL/2 + 1); longitudes i 360/nlon.
+                      *   ldshiftll != 0: kdgl = nlat (even); NDGL = kdgl rows at 90 - (j-1/2) 180/nlat, longitudes (i+1/2) 360/nlon.
+                      * The series is evaluated exactly on these rows (the reference interpolates from a Gaussian grid).  Such a
+                      * handle keeps no Gaussian weights and no panels of the direct transform: it serves emi_inv_trans with
+                      * ldlatlon, the DIST_ / GATH_ routines, SPECNORM, TRANS_INQ and TRANS_RELEASE; emi_inv_trans without
+                      * ldlatlon, emi_dir_trans, both adjoints, emi_gpnorm and CDIO_LEGPOL return EMI_ERR_UNSUPPORTED.       */
 } emi_setup_t;
 int emi_setup(const emi_setup_t *cfg, int *kresol);
 
@@ -108,12 +118,13 @@ int emi_setup_legpol(const emi_setup_t *cfg, const emi_legpol_io_t *io, int *kre
 
 /* ---- TRANS_INQ (trans/cpu/external/trans_inq.F90:11-529), subset used by callers ----- */
 /* integer scalars: "nspec2" "nspec2g" "nspec2mx" "ngptot" "ngptotg" "ngptotmx" "nump" "ndgl" "nsmax"
- * "ndlon" "nproc" "myproc" "nfrstlat" "nlstlat"                                           */
+ * "ndlon" "nproc" "myproc" "nfrstlat" "nlstlat" "ldll" "lshiftll" (0 | 1; "ndgl" of an unshifted LDLL handle is KDGL + 2) */
 int emi_inq_int(int kresol, const char *name, int *value);
 /* integer arrays: "nloen"(ndgl) "nmen"(ndgl) "ndglu"(nsmax+1) "nasm0"(nsmax+1, 1-based as
  * D%NASM0, -99 for wavenumbers of other tasks) "myms"(nump) "procm"(nsmax+1) "latlo"(nproc+1) */
 int emi_inq_int_array(int kresol, const char *name, int *out, int len);
-/* real arrays: "rmu"/"pmu"(ndgl) "rgw"/"pgw"(ndgl)                                        */
+/* real arrays: "rmu"/"pmu"(ndgl) "rgw"/"pgw"(ndgl).  LDLL handle: "rmu"/"pmu" are the sines of its row latitudes,
+ * "rgw"/"pgw" are refused (EMI_ERR_UNSUPPORTED: it keeps no Gaussian weights)              */
 int emi_inq_real_array(int kresol, const char *name, double *out, int len);
 /* Legendre panel of zonal wavenumber m as the reference stores it, S%FA(m)%RPNMA/RPNMS
  * (trans/cpu/internal/suleg_mod.F90:609-615,891-897): column-major (ndglu x ncols), n
@@ -182,6 +193,8 @@ typedef struct {
                                * buffers): a call waits, on the device, for the previous call of that handle */
   const emi_extents_t *ext;   /* extents of the arrays above, NULL: unchecked                */
   const emi_vsets_t *vsets;   /* NPRTRV > 1: the V-set of every global field (nf_uv ... then count LOCAL fields) */
+  int ldlatlon;               /* LDLATLON: the output grid is the lat-lon grid of a handle set up with ldll (required on such a
+                               * handle, refused on a Gaussian one)                                                          */
 } emi_invtrans_t;
 int emi_inv_trans(int kresol, const emi_invtrans_t *args);
 
