@@ -20,7 +20,7 @@ import os
 import numpy as np
 
 __all__ = ["TransError", "setup_trans0", "setup_trans", "inv_trans", "dir_trans", "trans_inq", "specnorm",
-           "trans_release", "trans_end", "lib", "build"]
+           "trans_release", "trans_end", "lib", "build", "esetup_trans", "einv_trans", "edir_trans", "etrans_inq"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBPATH = os.path.join(_HERE, "libectrans_mi.so")
@@ -52,6 +52,11 @@ class _Setup(C.Structure):
     _fields_ = [("ksmax", C.c_int), ("kdgl", C.c_int), ("kloen", C.POINTER(C.c_int)), ("kdlon", C.c_int),
                 ("precision", C.c_int), ("lduseflt", C.c_int), ("ldll", C.c_int), ("ldstretch", C.c_int),
                 ("lduserpnm", C.c_int), ("ldshiftll", C.c_int)]
+
+
+class _ESetup(C.Structure):  # emi_esetup_t
+    _fields_ = [("kmsmax", C.c_int), ("ksmax", C.c_int), ("kdgl", C.c_int), ("kloen", C.POINTER(C.c_int)), ("kdlon", C.c_int),
+                ("kdgux", C.c_int), ("pexwn", C.c_double), ("peywn", C.c_double), ("precision", C.c_int)]
 
 
 class _Ext(C.Structure):  # emi_extents_t
@@ -149,6 +154,10 @@ def _bind(L):
     L.emi_inq_tasks.argtypes = [ip, ip]
     L.emi_inq_init.argtypes = [ip, dp]
     L.emi_set_nprtrv.argtypes = [C.c_int]
+    if hasattr(L, "emi_esetup"):  # (an older build loaded for an A/B run)
+        L.emi_esetup.argtypes = [C.POINTER(_ESetup), ip]
+        L.emi_einv_trans.argtypes = [C.c_int, C.POINTER(_Inv), C.c_void_p, C.c_void_p]
+        L.emi_edir_trans.argtypes = [C.c_int, C.POINTER(_Dir), C.c_void_p, C.c_void_p]
     return L
 
 
@@ -494,6 +503,135 @@ def dir_transad(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, 
     a.stream = stream
     _fill_vsets(a, keep, kvsetuv, kvsetsc, kvsetsc2, kvsetsc3a, kvsetsc3b, pgp3a, pgp3b)
     _chk(lib().emi_dir_transad(kresol, C.byref(a)))
+
+
+# ---------------------------------------------------------------------------------------------
+# ESETUP_TRANS / EINV_TRANS / EDIR_TRANS / ETRANS_INQ: the limited-area, bi-Fourier transforms (etrans/include/etrans/*.h).
+# INTEGRATION.md ("Limited-area transforms") holds the definitions.
+# ---------------------------------------------------------------------------------------------
+def esetup_trans(kmsmax, ksmax, kdgl, kdgux=None, kloen=None, kdlon=0, pexwn=1.0, peywn=1.0, precision=8, ldsplit=False,
+                 ktmax=None, pweight=None, ldgridonly=False, knoextzl=0, knoextzg=0, ldusefftw=False, ld_all_fftw=False):
+    """ESETUP_TRANS (esetup_trans.h); returns KRESOL, from the same numbering as ``setup_trans``.
+
+    kmsmax, ksmax: truncation in x and y; kdgl rows of one length (``kloen`` with equal entries, or ``kdlon``); pexwn, peywn: the
+    wavenumber units 2 pi / (ndlon dx), 2 pi / (kdgl dy).  ldusefftw, ld_all_fftw are accepted and have no effect; ldsplit: rows
+    are never split between tasks."""
+    who = "ESETUP_TRANS"
+    if precision not in (4, 8):
+        raise TransError("%s: precision must be 4 or 8" % who)
+    if pweight is not None:
+        raise TransError("%s: PWEIGHT (weighted distribution) is not supported" % who)
+    if ldgridonly:
+        raise TransError("%s: LDGRIDONLY is not supported" % who)
+    if knoextzl or knoextzg:
+        raise TransError("%s: KNOEXTZL / KNOEXTZG (no extension zone) are not supported" % who)
+    if ktmax is not None and int(ktmax) != int(ksmax):
+        raise TransError("%s: KTMAX /= KSMAX is not supported" % who)
+    cfg = _ESetup()
+    cfg.kmsmax, cfg.ksmax, cfg.kdgl, cfg.kdlon = int(kmsmax), int(ksmax), int(kdgl), int(kdlon)
+    cfg.kdgux = int(kdgl if kdgux is None else kdgux)
+    cfg.pexwn, cfg.peywn, cfg.precision = float(pexwn), float(peywn), int(precision)
+    keep = None
+    if kloen is not None:
+        keep = np.ascontiguousarray(kloen, dtype=np.int32)
+        if keep.size < kdgl:
+            raise TransError("%s: KLOEN TOO SHORT" % who)
+        cfg.kloen = keep.ctypes.data_as(C.POINTER(C.c_int))
+    kresol = C.c_int(0)
+    _chk(lib().emi_esetup(C.byref(cfg), C.byref(kresol)))
+    _PREC[kresol.value] = "float32" if precision == 4 else "float64"
+    return kresol.value
+
+
+def _mean_ptr(x, nuv, space, keep, nm):
+    if x is None:
+        return None
+    if x.ndim != 1 or x.shape[0] < nuv:
+        raise TransError("%s must have shape (nf_uv=%d,)" % (nm, nuv))
+    p, k = _ptr(x, space)
+    keep.append(k)
+    return p
+
+
+def einv_trans(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, pspsc3b=None, pspsc2=None, fspgl_proc=None,
+               ldscders=False, ldvorgp=False, lddivgp=False, lduvder=False, kproma=None, pgp=None, pgpuv=None, pgp3a=None,
+               pgp3b=None, pgp2=None, pmeanu=None, pmeanv=None, stream=None, kvsetuv=None, kvsetsc=None, kvsetsc2=None,
+               kvsetsc3a=None, kvsetsc3b=None, mem_space=None):
+    """EINV_TRANS (einv_trans.h): spectral -> grid point on a handle of ``esetup_trans``; arrays as ``inv_trans``.
+    pmeanu, pmeanv: (nf_uv,) arrays where the other arrays live, the mean wind (the (0, 0) coefficients of u and v).
+    mem_space: overrides the memory space derived from the arrays (EMI_MEM_AUTO; on the CPU emulator of the tests EMI_MEM_DEVICE uses
+    numpy arrays in place, the path device tensors take on a GPU)."""
+    if fspgl_proc is not None:
+        raise TransError("EINV_TRANS: FSPGL_PROC is not supported")
+    if any(k is not None for k in (kvsetuv, kvsetsc, kvsetsc2, kvsetsc3a, kvsetsc3b)) and _DIST.get("nprtrv", 1) > 1:
+        raise TransError("EINV_TRANS: KVSET arguments: V-sets are not available on a limited-area handle")
+    a, space, keep = _Inv(), [None, real_dtype(kresol)], []
+    nspec2, ngptot = trans_inq(kresol, "nspec2"), trans_inq(kresol, "ngptot")
+    nproma = int(kproma) if kproma else ngptot
+    _fill_spec(a, space, keep, pspvor, pspdiv, pspscalar, pspsc3a, pspsc3b, pspsc2, nspec2)
+    _fill_grid(a, space, keep, pgp, pgpuv, pgp3a, pgp3b, pgp2, nproma, (ngptot - 1) // nproma + 1,
+               (pspvor, pspdiv, pspscalar, pspsc3a, pspsc3b, pspsc2))
+    a.ldscders, a.ldvorgp, a.lddivgp, a.lduvder = int(ldscders), int(ldvorgp), int(lddivgp), int(lduvder)
+    a.kproma = nproma
+    mu, mv = _mean_ptr(pmeanu, a.nf_uv, space, keep, "PMEANU"), _mean_ptr(pmeanv, a.nf_uv, space, keep, "PMEANV")
+    a.mem_space = int(mem_space) if mem_space is not None else space[0] if space[0] is not None else EMI_MEM_HOST
+    a.stream = stream
+    _chk(lib().emi_einv_trans(kresol, C.byref(a), mu, mv))
+
+
+def edir_trans(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, pspsc3b=None, pspsc2=None, kproma=None,
+               pgp=None, pgpuv=None, pgp3a=None, pgp3b=None, pgp2=None, pmeanu=None, pmeanv=None, aux_proc=None, stream=None,
+               kvsetuv=None, kvsetsc=None, kvsetsc2=None, kvsetsc3a=None, kvsetsc3b=None, mem_space=None):
+    """EDIR_TRANS (edir_trans.h): grid point -> spectral on a handle of ``esetup_trans``; pmeanu, pmeanv receive the mean wind."""
+    if aux_proc is not None:
+        raise TransError("EDIR_TRANS: AUX_PROC is not supported")
+    if any(k is not None for k in (kvsetuv, kvsetsc, kvsetsc2, kvsetsc3a, kvsetsc3b)) and _DIST.get("nprtrv", 1) > 1:
+        raise TransError("EDIR_TRANS: KVSET arguments: V-sets are not available on a limited-area handle")
+    a, space, keep = _Dir(), [None, real_dtype(kresol)], []
+    nspec2, ngptot = trans_inq(kresol, "nspec2"), trans_inq(kresol, "ngptot")
+    nproma = int(kproma) if kproma else ngptot
+    _fill_spec(a, space, keep, pspvor, pspdiv, pspscalar, pspsc3a, pspsc3b, pspsc2, nspec2)
+    _fill_grid(a, space, keep, pgp, pgpuv, pgp3a, pgp3b, pgp2, nproma, (ngptot - 1) // nproma + 1,
+               (pspvor, pspdiv, pspscalar, pspsc3a, pspsc3b, pspsc2))
+    a.kproma = nproma
+    mu, mv = _mean_ptr(pmeanu, a.nf_uv, space, keep, "PMEANU"), _mean_ptr(pmeanv, a.nf_uv, space, keep, "PMEANV")
+    a.mem_space = int(mem_space) if mem_space is not None else space[0] if space[0] is not None else EMI_MEM_HOST
+    a.stream = stream
+    _chk(lib().emi_edir_trans(kresol, C.byref(a), mu, mv))
+
+
+_E_INT_SCALARS = ("nspec", "nspec2", "nspec2g", "nspec2mx", "nump", "ngptot", "ngptotg", "ngptotmx", "nprtrw", "mysetw", "mysetv",
+                  "nsmax", "nmsmax", "ndgl", "ndlon", "ndgux", "ldlam", "nfrstlat", "nlstlat", "nproc", "myproc")
+_E_INT_ARRAYS = {"myms": "nump", "kntmp": "m", "ncpl2m": "m", "ncpl4m": "m", "npme": "m", "nesm0": "m", "ndim0g": "m", "nallms": "m",
+                 "procm": "m", "numpp": "w", "nptrms": "w", "npossp": "w+1", "latlo": "w+1", "nloen": "ndgl", "fftwork": "ndgl"}
+
+
+def etrans_inq(kresol, name):
+    """ETRANS_INQ (etrans_inq.h): one quantity of a limited-area handle by lower-case name.  Arrays over the x-wavenumbers have
+    KMSMAX + 1 entries (positions 1-based as in the reference, -99 in "nesm0" for the wavenumbers of other tasks); "latlo" holds the
+    0-based first row of every task's band (KPTRFRSTLAT - 1) and NDGL; "rlepinm" is FALD%RLEPINM."""
+    L = lib()
+    name = name.lower()
+    v = C.c_int(0)
+    _chk(L.emi_inq_int(kresol, b"ldlam", C.byref(v)))
+    if not v.value:
+        raise TransError("ETRANS_INQ: resolution %d is not a limited-area handle (ESETUP_TRANS)" % kresol)
+    if name in _E_INT_SCALARS:
+        _chk(L.emi_inq_int(kresol, name.encode(), C.byref(v)))
+        return v.value
+    q = lambda n: etrans_inq(kresol, n)
+    if name in _E_INT_ARRAYS:
+        dims = {"nump": "nump", "ndgl": "ndgl"}
+        k = _E_INT_ARRAYS[name]
+        n = q("nmsmax") + 1 if k == "m" else q("nprtrw") if k == "w" else q("nprtrw") + 1 if k == "w+1" else q(dims[k])
+        out = np.zeros(n, dtype=np.int32)
+        _chk(L.emi_inq_int_array(kresol, name.encode(), out.ctypes.data_as(C.POINTER(C.c_int)), out.size))
+        return out
+    if name in ("rlepinm", "plepinm"):
+        out = np.zeros(q("nspec2g") // 4)
+        _chk(L.emi_inq_real_array(kresol, name.encode(), out.ctypes.data_as(C.POINTER(C.c_double)), out.size))
+        return out
+    raise TransError("ETRANS_INQ: unknown quantity %r" % name)
 
 
 def specnorm(kresol, pspec, kvset=None):

@@ -289,6 +289,18 @@ struct Plan {  // owns its device memory; whoever drops a plan that has run some
   // LDLL: a regular lat-lon grid (rmu = the sines of its rows, no Gaussian weights, no PT panels: INV_TRANS(LDLATLON) only);
   // shiftll: LDSHIFTLL, rows and longitudes offset by half a cell (the longitude half by g.llphase in k_prepack_inv)
   bool ldll = false, shiftll = false;
+  // ESETUP_TRANS: a limited-area (bi-Fourier) handle.  nsmax holds KMSMAX, the truncation in x (the wavenumbers that are distributed and
+  // that the x-direction kernels cut at); lam_n = KSMAX, the truncation in y.  Full grid of NDGL rows of NDLON points, NMEN = KMSMAX on
+  // every row; no Legendre panels, no Gaussian latitudes: rw holds 1 / NDGL and racthe EXWN on every row, which makes the x-direction
+  // kernels' per-row weight the normalisation and their GM_EWDER factor i m EXWN.
+  bool lam = false;
+  int lam_n = 0, kdgux = 0;
+  double exwn = 0.0, eywn = 0.0;
+  std::vector<int> kntmp;           // [KMSMAX + 1] the ellipse (ellips.F90:71-97)
+  std::vector<int> l_kntmp, nesm0;  // [nump] of the local wavenumbers; nesm0 0-based
+  LamDev lamdev{};
+  int lam_nthr = 0;
+  size_t lam_lds = 0;
   double ra = 6371229.0;
   // ---- global geometry (identical on every task)
   std::vector<int> nloen, nmen, ndglu, procm;  // procm[m]: owning task (0-based) of wavenumber m
@@ -882,6 +894,51 @@ static int build_fft_plans(Plan &P) {
     }
     pl.lds_class = cls;
     idx[n] = P.planid[j] = (int)P.fplans.size();
+    P.fplans.push_back(pl);
+  }
+  if (P.lam) {
+    // The y-direction of a limited-area handle: ONE complex plan of length NDGL for the generic in-LDS passes (k_lam_inv, k_lam_dir) --
+    // mixed radix where NDGL is a product of 2, 3, 4, 5, 7, 8, Bluestein otherwise -- with the tables every plan has.  No launch class:
+    // the kernels take it by number (LamDev::yplan).
+    FftPlanDev pl{};
+    pl.n = pl.sz = pl.S = P.ndgl;
+    pl.cmode = 1;
+    std::vector<int> fac;
+    pl.blue = !emi::factorize_smooth(pl.sz, fac);
+    if (pl.blue) {
+      pl.S = emi::next_235(2 * pl.sz - 1);
+      emi::factorize_smooth(pl.S, fac);
+    }
+    // [field][point] work array of an even number of fields (u and v of a wind pair share a workgroup in k_lam_dir), an odd number of
+    // complex elements from field to field; up to 80 KiB per workgroup (two per CU) where that holds two fields, the whole LDS otherwise
+    const int fs = FFT_LDS_ELEMS(pl.S) + 1, fs_max = 160 * 1024 / (4 * P.esz);
+    if (fs > fs_max || pl.S > 65535 || fac.size() > 14)
+      EMI_FAIL(EMI_ERR_UNSUPPORTED,
+               "ESETUP_TRANS: KDGL = %d NEEDS A WORK ARRAY OF %d COMPLEX NUMBERS PER FIELD (KDGL WHERE IT FACTORISES IN 2, 3, 5, 7, ELSE THE CONVOLUTION LENGTH ABOVE 2 KDGL); THE "
+               "Y-DIRECTION KERNELS HOLD TWO FIELDS IN THE 160 KIB OF LDS: AT MOST %d",
+               P.ndgl, fs, fs_max);
+    pl.nfac = (int)fac.size();
+    for (int i = 0; i < pl.nfac; i++) pl.fac[i] = fac[i];
+    const size_t per_field = (size_t)fs * 2 * P.esz;
+    pl.fbk = std::max(2, std::min(16, (int)(80 * 1024 / per_field) / 2 * 2));
+    const FftShared &sh = fft_share_tables(pl, sidx, shared, nt);
+    pl.tw_off = sh.tw_off;
+    pl.perm_off = sh.perm_off;
+    for (int ip = 0; ip < pl.nfac; ip++) pl.ptw_off[ip] = sh.ptw_off[ip];
+    pl.rtw_off = (int)nt.rtw;
+    nt.rtw += pl.sz + 1;
+    if (pl.blue) {
+      pl.chirp_off = (int)nt.chirp;
+      nt.chirp += pl.sz;
+      pl.bhat_off = (int)nt.bhat;
+      nt.bhat += pl.S;
+    }
+    pl.lds_class = -1;
+    P.lamdev.yplan = (int)P.fplans.size();
+    P.lamdev.fbk = pl.fbk;
+    P.lamdev.fs = fs;
+    P.lam_lds = (size_t)pl.fbk * per_field;
+    P.lam_nthr = std::min(512, fft_threads(P.lam_lds));  // (EMI_KERNEL_LAM: at most 512 threads)
     P.fplans.push_back(pl);
   }
   // ---- pass 2: fill the tables
@@ -1585,6 +1642,123 @@ extern "C" int emi_setup_legpol(const emi_setup_t *cfg, const emi_legpol_io_t *i
 
 extern "C" int emi_setup(const emi_setup_t *cfg, int *kresol) { return emi_setup_legpol(cfg, nullptr, kresol); }
 
+// ------------------------------------------------------------------------------------------
+// ESETUP_TRANS (etrans/include/etrans/esetup_trans.h): a limited-area, bi-Fourier handle.  Same stages as SETUP_TRANS without the
+// Legendre ones: arguments, geometry (a full grid, NMEN = KMSMAX), distribution (the zig-zag of SUWAVEDI over the x-wavenumbers, as
+// suemp_trans_preleg_mod.F90:106-132; whole-row bands), local tables (the ellipse), row tables, device tables, FFT plans of both directions.
+// ------------------------------------------------------------------------------------------
+static void lam_ellipse(int M, int N, std::vector<int> &kntmp) {  // ellips.F90:71-97, in double
+  kntmp.assign(M + 1, 0);
+  for (int m = 1; m < M; m++) kntmp[m] = (int)((double)N / (double)M * std::sqrt(std::max(0.0, (double)(M * M - m * m))) + 1.0e-10);
+  kntmp[0] = N;
+  if (M > 0) kntmp[M] = 0;
+}
+
+extern "C" int emi_esetup(const emi_esetup_t *cfg, int *kresol) {
+  EmiRange rg_setup(EMI_LBL_SETUP);
+  if (!G.init) EMI_FAIL(EMI_ERR_STATE, "ESETUP_TRANS: SETUP_TRANS0 HAS TO BE CALLED BEFORE ESETUP_TRANS");
+  if (!cfg) EMI_FAIL(EMI_ERR_ARG, "emi_esetup: null config");
+  if (cfg->kdgl < 2) EMI_FAIL(EMI_ERR_ARG, "ESETUP_TRANS: KDGL = %d, AT LEAST 2 ROWS ARE NEEDED", cfg->kdgl);
+  for (int j = 1; cfg->kloen && j < cfg->kdgl; j++)
+    if (cfg->kloen[j] != cfg->kloen[0])
+      EMI_FAIL(EMI_ERR_ARG, "ESETUP_TRANS: KLOEN MUST HOLD ONE ROW LENGTH (KLOEN(%d) = %d, KLOEN(1) = %d)", j + 1, cfg->kloen[j], cfg->kloen[0]);
+  const int ndlon = cfg->kloen ? cfg->kloen[0] : cfg->kdlon;
+  if (ndlon < 2) EMI_FAIL(EMI_ERR_ARG, "ESETUP_TRANS: KLOEN INVALID (ROW LENGTH %d)", ndlon);
+  if (cfg->kmsmax < 0 || cfg->ksmax < 0) EMI_FAIL(EMI_ERR_ARG, "ESETUP_TRANS: KMSMAX = %d, KSMAX = %d", cfg->kmsmax, cfg->ksmax);
+  // the spectrum of a row (of a column) ends below its Nyquist wavenumber: C(n) and C(NDGL - n) are different entries
+  if (2 * cfg->kmsmax >= ndlon) EMI_FAIL(EMI_ERR_ARG, "ESETUP_TRANS: KMSMAX = %d MUST BE BELOW HALF THE ROW LENGTH %d", cfg->kmsmax, ndlon);
+  if (2 * cfg->ksmax >= cfg->kdgl) EMI_FAIL(EMI_ERR_ARG, "ESETUP_TRANS: KSMAX = %d MUST BE BELOW HALF OF KDGL = %d", cfg->ksmax, cfg->kdgl);
+  if (cfg->precision != 0 && cfg->precision != 8 && cfg->precision != 4)
+    EMI_FAIL(EMI_ERR_ARG, "emi_esetup: precision must be 8 (fp64, the _dp library) or 4 (fp32, _sp), got %d", cfg->precision);
+  if (G.nprtrv > 1) EMI_FAIL(EMI_ERR_UNSUPPORTED, "ESETUP_TRANS: NPRTRV = %d: V-SETS ARE NOT AVAILABLE ON A LIMITED-AREA HANDLE", G.nprtrv);
+  if (G.nproc > 1 && !G.a2a) EMI_FAIL(EMI_ERR_STATE, "ESETUP_TRANS: %d tasks but no all-to-all-v hook registered (emi_set_alltoallv)", G.nproc);
+  const int slot = first_free_slot();
+  if (slot < 0) EMI_FAIL(EMI_ERR_STATE, "ESETUP_TRANS:IDEF_RESOL > NMAX_RESOL");
+  std::unique_ptr<Plan> pp(new Plan());
+  Plan &P = *pp;
+  const int M = cfg->kmsmax, N = cfg->ksmax, L = cfg->kdgl, NP = G.nproc;
+  P.lam = true;
+  P.nsmax = M, P.lam_n = N, P.ndgl = L, P.ndgnh = (L + 1) / 2, P.kdgux = cfg->kdgux;
+  P.exwn = cfg->pexwn, P.eywn = cfg->peywn;
+  P.ra = G.ra;
+  P.esz = cfg->precision == 4 ? 4 : 8;
+  P.nproc = NP, P.me = G.myproc - 1, P.nprv = 1, P.mev = 0;
+  if (NP > L || NP > M + 1) EMI_FAIL(EMI_ERR_ARG, "ESETUP_TRANS: too many tasks (%d) for KDGL=%d, KMSMAX=%d", NP, L, M);
+  // ---- geometry
+  P.nloen.assign(L, ndlon);
+  P.nmen.assign(L, M);
+  P.ndglu.assign(M + 1, L);
+  P.rw.assign(L, 1.0 / (double)L);  // with the x-kernels' 1 / NLOEN: forward transforms scaled by 1 / (NDLON NDGL)
+  P.racthe.assign(L, P.exwn);       // GM_EWDER of the x-kernels: i m EXWN (efsc_mod.F90)
+  P.cos2.assign(L, 1.0);
+  std::vector<long long> cum(L + 1, 0);
+  for (int j = 0; j < L; j++) cum[j + 1] = cum[j] + ndlon;
+  if (cum[L] > 2000000000LL) EMI_FAIL(EMI_ERR_UNSUPPORTED, "grid too large for 32-bit point offsets");
+  P.ngptotg = (int)cum[L];
+  lam_ellipse(M, N, P.kntmp);
+  P.nspec2g = 0;
+  for (int m = 0; m <= M; m++) P.nspec2g += 4 * (P.kntmp[m] + 1);
+  // ---- distribution: the zig-zag over m; bands of whole rows, the first mod(NDGL, NPRTRW) of them one row longer (what
+  // suemp_trans_preleg_mod.F90:187-197 sets out to do)
+  int rc;
+  if ((rc = setup_distribution(M, L, P.nloen, cum, NP, 1, P.procm, P.latlo, P.vlat))) return rc;
+  for (int r = 0; r <= NP; r++) P.latlo[r] = r * (L / NP) + std::min(r, L % NP);
+  // ---- this task's share
+  SetupTables T;
+  P.lat0 = P.latlo[P.me];
+  P.nlat = P.latlo[P.me + 1] - P.lat0;
+  P.ngptot = (int)(cum[P.latlo[P.me + 1]] - cum[P.lat0]);
+  for (int m = 0; m <= M; m++)
+    if (P.procm[m] == P.me) P.mval.push_back(m);
+  P.nump = (int)P.mval.size();
+  const int NU = P.nump, NL = P.nlat;
+  int ipos = 0;
+  for (int ml = 0; ml < NU; ml++) {
+    P.l_kntmp.push_back(P.kntmp[P.mval[ml]]);
+    P.nesm0.push_back(ipos);
+    ipos += 4 * (P.kntmp[P.mval[ml]] + 1);
+  }
+  P.nspec2 = ipos;
+  P.lbase.assign(NU + 1, 0);  // no hemispheres: the row tables of the y-side are lamdev.rowbase
+  P.l_nmen.assign(NL, M);
+  P.l_gpoff.assign(NL, 0);
+  P.l_fbase.assign(NL + 1, 0);
+  T.l_rw.assign(NL, 1.0 / (double)L);
+  T.l_racthe.assign(NL, P.exwn);
+  for (int jl = 0; jl < NL; jl++) {
+    P.l_gpoff[jl] = jl * ndlon;
+    P.l_fbase[jl + 1] = P.l_fbase[jl] + M + 1;
+  }
+  P.frows = P.l_fbase[NL];
+  P.lrows = (long long)NU * L;
+  P.wrows_total = 0;
+  const bool exchange_order = NP > 1 || (test_paths() & 1);
+  if ((rc = setup_row_tables(P, exchange_order, T))) return rc;
+  std::vector<int> rowbase(L, 0);
+  if (exchange_order) {  // block d of the y-side buffer: the rows (row of band d, local wavenumber), row-major -- the order of setup_row_tables
+    for (int d = 0; d < NP; d++)
+      for (int j = P.latlo[d]; j < P.latlo[d + 1]; j++) rowbase[j] = (int)P.leg_disp[d] + (j - P.latlo[d]) * NU;
+  } else {
+    for (int j = 0; j < L; j++) rowbase[j] = j * (M + 1);
+  }
+  // ---- device tables
+  EmiGeomDev &g = P.g;
+  g.nsmax = M, g.nump = NU, g.nlat = NL, g.ngptot = P.ngptot;
+  LamDev &ld = P.lamdev;
+  ld.ndgl = L, ld.exwn = P.exwn, ld.eywn = P.eywn;
+  if (upload(P.dev_allocs, P.mval, &g.mval) || upload(P.dev_allocs, P.l_nmen, &g.nmen) || upload(P.dev_allocs, P.l_gpoff, &g.gpoff) ||
+      upload(P.dev_allocs, P.l_fbase, &g.fbase) || upload(P.dev_allocs, T.fftrow, &g.fftrow) || upload(P.dev_allocs, T.l_rw, &g.rw) ||
+      upload(P.dev_allocs, T.l_racthe, &g.racthe) || upload(P.dev_allocs, P.l_kntmp, &ld.kntmp) || upload(P.dev_allocs, P.nesm0, &ld.nesm0) ||
+      upload(P.dev_allocs, rowbase, &ld.rowbase))
+    return EMI_ERR_RUNTIME;
+  if (!T.rowtable) g.fftrow = nullptr;
+  if ((rc = build_fft_plans(P))) return rc;
+  emi_stream_sync(0);
+  G.plans[slot] = std::move(pp);
+  if (kresol) *kresol = slot + 1;
+  return EMI_SUCCESS;
+}
+
 extern "C" int emi_set_alltoallv(emi_alltoallv_fn fn, void *user) {
   G.a2a = fn;
   G.a2a_user = user;
@@ -1634,13 +1808,13 @@ extern "C" int emi_inq_int(int kresol, const char *name, int *value) {
   else if (s == "nspec2mx") {
     int mx = 0;
     std::vector<int> cnt(P->nproc, 0);
-    for (int m = 0; m <= P->nsmax; m++) cnt[P->procm[m]] += 2 * (P->nsmax - m + 1);
+    for (int m = 0; m <= P->nsmax; m++) cnt[P->procm[m]] += P->lam ? 4 * (P->kntmp[m] + 1) : 2 * (P->nsmax - m + 1);
     for (int c : cnt) mx = std::max(mx, c);
     *value = mx;
-  } else if (s == "nspec")
-    *value = P->nspec2 / 2;
+  } else if (s == "nspec")  // (D%NSPEC = D%NSPEC2 on a limited-area handle, suemp_trans_preleg_mod.F90:146)
+    *value = P->lam ? P->nspec2 : P->nspec2 / 2;
   else if (s == "nspecg")
-    *value = P->nspec2g / 2;
+    *value = P->lam ? P->nspec2g : P->nspec2g / 2;
   else if (s == "ngptot")  // this task's grid points: its sub-band with V-sets, else its band
     *value = P->nprv > 1 ? (int)P->vpoints(P->me, P->mev) : P->ngptot;
   else if (s == "ngptot_band")  // grid points of the whole band of this task's W-set (the FFT work of its V-set)
@@ -1656,9 +1830,16 @@ extern "C" int emi_inq_int(int kresol, const char *name, int *value) {
     *value = P->nump;
   else if (s == "ndgl")
     *value = P->ndgl;
-  else if (s == "nsmax")
+  else if (s == "nsmax")  // KSMAX: on a limited-area handle the truncation in y ("nmsmax": in x)
+    *value = P->lam ? P->lam_n : P->nsmax;
+  else if (s == "nmsmax")
     *value = P->nsmax;
-  else if (s == "ldll")
+  else if (s == "ldlam")
+    *value = P->lam ? 1 : 0;
+  else if (s == "ndgux") {
+    if (!P->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "ETRANS_INQ: %s: resolution %d is not a limited-area handle (ESETUP_TRANS)", s.c_str(), kresol);
+    *value = P->kdgux;
+  } else if (s == "ldll")
     *value = P->ldll ? 1 : 0;
   else if (s == "lshiftll" || s == "ldshiftll")
     *value = P->shiftll ? 1 : 0;
@@ -1691,7 +1872,46 @@ extern "C" int emi_inq_int_array(int kresol, const char *name, int *out, int len
   std::string s(name ? name : "");
   const std::vector<int> *v = nullptr;
   std::vector<int> tmp;
-  if (s == "nloen")
+  const bool lam_name = s == "kntmp" || s == "nesm0" || s == "ncpl2m" || s == "ncpl4m" || s == "npme" || s == "numpp" || s == "npossp" || s == "nallms" ||
+                        s == "nptrms" || s == "ndim0g";
+  if (lam_name && !P->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "ETRANS_INQ: %s: resolution %d is not a limited-area handle (ESETUP_TRANS)", s.c_str(), kresol);
+  if (P->lam && (s == "ndglu" || s == "nasm0"))
+    EMI_FAIL(EMI_ERR_UNSUPPORTED, "TRANS_INQ: %s: resolution %d is a limited-area handle (ESETUP_TRANS): it has no Legendre transform", s.c_str(), kresol);
+  if (lam_name) {
+    // the tables of suemp_trans_preleg_mod.F90:76-177 over the x-wavenumbers 0 .. KMSMAX; positions 1-based as there
+    const int M = P->nsmax, NP = P->nproc;
+    std::vector<int> numpp(NP, 0), ispec(NP, 0), nptrms(NP, 1);
+    for (int m = 0; m <= M; m++) numpp[P->procm[m]]++, ispec[P->procm[m]] += P->kntmp[m] + 1;
+    for (int a = 1; a < NP; a++) nptrms[a] = nptrms[a - 1] + numpp[a - 1];
+    std::vector<int> nallms(M + 1, 0), ic(NP, 0);
+    for (int m = 0; m <= M; m++) nallms[ic[P->procm[m]]++ + nptrms[P->procm[m]] - 1] = m;
+    if (s == "kntmp")
+      tmp = P->kntmp;
+    else if (s == "ncpl2m" || s == "ncpl4m") {
+      tmp.resize(M + 1);
+      for (int m = 0; m <= M; m++) tmp[m] = (s == "ncpl2m" ? 2 : 4) * (P->kntmp[m] + 1);
+    } else if (s == "npme") {
+      tmp.assign(M + 1, 1);
+      for (int m = 1; m <= M; m++) tmp[m] = tmp[m - 1] + P->kntmp[m - 1] + 1;
+    } else if (s == "nesm0") {  // -99 for the wavenumbers of other tasks
+      tmp.assign(M + 1, -99);
+      for (int ml = 0; ml < P->nump; ml++) tmp[P->mval[ml]] = P->nesm0[ml] + 1;
+    } else if (s == "numpp")
+      tmp = numpp;
+    else if (s == "npossp") {
+      tmp.assign(NP + 1, 1);
+      for (int a = 1; a <= NP; a++) tmp[a] = tmp[a - 1] + 4 * ispec[a - 1];
+    } else if (s == "nallms")
+      tmp = nallms;
+    else if (s == "nptrms")
+      tmp = nptrms;
+    else {  // ndim0g
+      tmp.assign(M + 1, 0);
+      int ipos = 1;
+      for (int m : nallms) tmp[m] = ipos, ipos += 4 * (P->kntmp[m] + 1);
+    }
+    v = &tmp;
+  } else if (s == "nloen")
     v = &P->nloen;
   else if (s == "nmen" || s == "nmeng")
     v = &P->nmen;
@@ -1729,7 +1949,19 @@ extern "C" int emi_inq_real_array(int kresol, const char *name, double *out, int
   if (!P) EMI_FAIL(EMI_ERR_STATE, "TRANS_INQ: unknown resolution %d", kresol);
   std::string s(name ? name : "");
   const std::vector<double> *v = nullptr;
-  if (s == "rmu" || s == "pmu")
+  std::vector<double> tmp;
+  if (P->lam && s != "rlepinm" && s != "plepinm")
+    EMI_FAIL(EMI_ERR_UNSUPPORTED, "TRANS_INQ: %s: resolution %d is a limited-area handle (ESETUP_TRANS): it has no Gaussian latitudes, weights or Laplacian table", s.c_str(), kresol);
+  if (s == "rlepinm" || s == "plepinm") {
+    // FALD%RLEPINM (suemp_trans_preleg_mod.F90:86-100): 1 / -((m EXWN)^2 + (n EYWN)^2) at NPME(m) + n, 0 for (0, 0)
+    if (!P->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "ETRANS_INQ: %s: resolution %d is not a limited-area handle (ESETUP_TRANS)", s.c_str(), kresol);
+    for (int m = 0; m <= P->nsmax; m++)
+      for (int n = 0; n <= P->kntmp[m]; n++) {
+        const double l = -((double)m * m * P->exwn * P->exwn + (double)n * n * P->eywn * P->eywn);
+        tmp.push_back(l != 0.0 ? 1.0 / l : 0.0);
+      }
+    v = &tmp;
+  } else if (s == "rmu" || s == "pmu")
     v = &P->rmu;
   else if (s == "rgw" || s == "pgw" || s == "rw") {
     if (P->ldll) EMI_FAIL(EMI_ERR_UNSUPPORTED, "TRANS_INQ: %s: a handle set up with LDLL keeps no Gaussian weights", s.c_str());
@@ -1753,6 +1985,7 @@ extern "C" int emi_inq_real_array(int kresol, const char *name, double *out, int
 extern "C" int emi_inq_legendre(int kresol, int m, int symmetric, double *out, int *nrows, int *ncols) {
   Plan *P = get_plan(kresol);
   if (!P) EMI_FAIL(EMI_ERR_STATE, "TRANS_INQ: unknown resolution %d", kresol);
+  if (P->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "TRANS_INQ: emi_inq_legendre: resolution %d is a limited-area handle (ESETUP_TRANS): it has no Legendre polynomials", kresol);
   if (m < 0 || m > P->nsmax) EMI_FAIL(EMI_ERR_ARG, "emi_inq_legendre: m out of range");
   if (P->procm[m] != P->me) EMI_FAIL(EMI_ERR_ARG, "emi_inq_legendre: wavenumber %d belongs to task %d", m, P->procm[m] + 1);
   const int ml = (int)(std::lower_bound(P->mval.begin(), P->mval.end(), m) - P->mval.begin());
@@ -1783,6 +2016,7 @@ extern "C" int emi_inq_legendre(int kresol, int m, int symmetric, double *out, i
 static int legpol_write(int kresol, const char *fname) {
   Plan *P = get_plan(kresol);
   if (!P) EMI_FAIL(EMI_ERR_STATE, "WRITE_LEGPOL: unknown resolution %d", kresol);
+  if (P->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "WRITE_LEGPOL: resolution %d is a limited-area handle (ESETUP_TRANS): it has no Legendre polynomials", kresol);
   FILE *f = fopen(fname, "wb");
   if (!f) EMI_FAIL(EMI_ERR_ARG, "WRITE_LEGPOL: BYTES_IO_OPEN FAILED (%s)", fname);
   int head[4];
@@ -2291,6 +2525,10 @@ static int set_lds_attrs() {
   EMI_CHECK(hipFuncSetAttribute((const void *)emi_f32::k_fft_dir_hot<pc_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   EMI_HOT_PLAN_LIST(EMI_HOT_ATTR)
 #undef EMI_HOT_ATTR
+  EMI_CHECK(hipFuncSetAttribute((const void *)emi_f64::k_lam_inv, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  EMI_CHECK(hipFuncSetAttribute((const void *)emi_f64::k_lam_dir, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  EMI_CHECK(hipFuncSetAttribute((const void *)emi_f32::k_lam_inv, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  EMI_CHECK(hipFuncSetAttribute((const void *)emi_f32::k_lam_dir, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   EMI_CHECK(hipFuncSetAttribute((const void *)emi_f64::k_fft_inv, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   EMI_CHECK(hipFuncSetAttribute((const void *)emi_f64::k_fft_dir, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   EMI_CHECK(hipFuncSetAttribute((const void *)emi_f32::k_fft_inv, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -2419,13 +2657,14 @@ struct Call {
   int gp_nfld;
   int ldscders, ldvorgp, lddivgp, lduvder;  // LDSCDERS, LDVORGP, LDDIVGP, LDUVDER: 0 from an emi_dirtrans_t
   int ldlatlon;                             // LDLATLON: 0 from an emi_dirtrans_t
+  void *meanu, *meanv;                      // EINV_TRANS / EDIR_TRANS: PMEANU / PMEANV(nf_uv), reals of the library precision where the other arrays live
 };
 template <class A>
 static Call to_call(const A &a) {
   Call c{a.mem_space, (emi_stream_t)a.stream, a.ext, a.vsets, a.kproma,
          (void *)a.spvor, (void *)a.spdiv, (void *)a.spscalar, (void *)a.spsc3a, (void *)a.spsc3b, (void *)a.spsc2,
          a.nf_uv, a.nf_scalar, a.sc3a_nlev, a.sc3a_nvar, a.sc3b_nlev, a.sc3b_nvar, a.nf_sc2,
-         (void *)a.gp, (void *)a.gpuv, (void *)a.gp3a, (void *)a.gp3b, (void *)a.gp2, a.gp_nfld, 0, 0, 0, 0, 0};
+         (void *)a.gp, (void *)a.gpuv, (void *)a.gp3a, (void *)a.gp3b, (void *)a.gp2, a.gp_nfld, 0, 0, 0, 0, 0, nullptr, nullptr};
   if constexpr (std::is_same<A, emi_invtrans_t>::value)
     c.ldscders = a.ldscders, c.ldvorgp = a.ldvorgp, c.lddivgp = a.lddivgp, c.lduvder = a.lduvder, c.ldlatlon = a.ldlatlon;
   return c;
@@ -2584,7 +2823,7 @@ static int run_batches(Plan &P, emi_stream_t st, bool inverse, bool piped, int b
   // Legendre tile maps per batch: a batch with fewer fields than the row width (the last one of a call) only
   // gets the column tiles that hold fields (built before anything is queued or forked: a new map is a blocking upload)
   for (Batch &bt : bats)
-    if (leg_tilemaps(P, bt.ntiles, &bt.maps)) return EMI_ERR_RUNTIME;
+    if (!P.lam && leg_tilemaps(P, bt.ntiles, &bt.maps)) return EMI_ERR_RUNTIME;
   if (upload_desc(P, hdesc, st)) return EMI_ERR_RUNTIME;
   emi_stream_t sA = st, sB = st, sX = st;
   if (piped) {
@@ -2709,6 +2948,16 @@ static int inv_pipeline(Plan &P, const Call &d, const Fields &f, std::vector<Gri
     EmiRange rg(EMI_LBL_LTINV);  // GSTATS 102: PRFI1B / VDTUV / SPNSDE + LEINV + ASRE1B
     const int ldw = bt.ldw, bfpad_b = bt.ldw / 2;  // this batch's row width
     const SpecSrc *d_bl = (const SpecSrc *)((char *)P.d_desc + bt.off_s);
+    if (P.lam) {
+      // limited-area handle: EPRFI1B / EVDTUV / ESPNSDE + ELEINV + EASRE1B in one kernel, from the caller's arrays to the Fourier buffer;
+      // the y-direction FFT is timed in the Legendre slot
+      const int nchunk = (bt.ns + P.lamdev.fbk - 1) / P.lamdev.fbk;
+      const int ivl = g_pt.start(1, s);
+      EMI_LAUNCH_P(P.esz, k_lam_inv, (long long)P.nump * nchunk, P.lam_nthr, P.lam_lds, s, P.g, P.lamdev, P.ftab, d_bl, bt.ns, (const RT *)d.meanu, (const RT *)d.meanv,
+                   (RT *)FBl, ldw, nchunk);
+      g_pt.stop(ivl, s);
+      return 0;
+    }
     int iv = g_pt.start(0, s);
     {
       long long nblk = (long long)P.wrows_total * ((bfpad_b + 255) / 256);
@@ -2786,7 +3035,7 @@ static int dir_pipeline(Plan &P, const Call &d, const Fields &f, const std::vect
   int maxb = 0;
   for (auto &b : batches) maxb = std::max(maxb, (int)b.size());
   const int bfpad = roundup(maxb, 64);  // every batch has its own row width (2 x its fields rounded up to 64)
-  const bool fuse_dir = !(test_paths() & 4);  // plain-copy fields leave k_leg_dir's epilogue straight for the caller's arrays
+  const bool fuse_dir = !(test_paths() & 4) && !P.lam;  // plain-copy fields leave k_leg_dir's epilogue straight for the caller's arrays
   std::vector<Batch> bats;
   std::vector<char> hdesc;
   for (auto &b : batches) {
@@ -2850,6 +3099,17 @@ static int dir_pipeline(Plan &P, const Call &d, const Fields &f, const std::vect
     EmiRange rgl(EMI_LBL_LTDIR);  // GSTATS 103: PRFI2B + LEDIR + UVTVD + UPDSP
     const int ldw = bt.ldw;  // this batch's row width
     const long long lrows_call = P.nproc > 1 ? P.lrows : P.frows;
+    if (P.lam) {
+      // limited-area handle: EPRFI2B + ELEDIR + EUVTVD + EUPDSP in one kernel, from the Fourier buffer to the caller's arrays (bt.ns outputs
+      // in the order of their source fields, bt.ng fields in the buffer); timed in the Legendre slot
+      const int nchunk = (bt.ng + P.lamdev.fbk - 1) / P.lamdev.fbk;
+      const int ivl = g_pt.start(1, s);
+      EMI_LAUNCH_P(P.esz, k_lam_dir, (long long)P.nump * nchunk, P.lam_nthr, P.lam_lds, s, P.g, P.lamdev, P.ftab, (const SpecDst *)((char *)P.d_desc + bt.off_s), bt.ns, bt.ng,
+                   (RT *)d.meanu, (RT *)d.meanv, (const RT *)FBl, ldw, nchunk);
+      g_pt.stop(ivl, s);
+      done();
+      return 0;
+    }
     int iv = g_pt.start(1, s);
     // the zero row of this batch: row `lrows_call` in the batch's own row width (the buffer held other data before)
     emi_dev_memset(FBl + (size_t)lrows_call * ldw * P.esz, 0, (size_t)ldw * P.esz, s);
@@ -2892,14 +3152,24 @@ static int wset_transform(Plan &P, const Call &c, bool inverse, bool adj, const 
   const bool gpad = gsz != (size_t)P.ngptot;  // last NPROMA block padded: those elements are not written
   Call d;
   int rc = stage(P, hs, c, who, inverse, host && f.nuv, f, gsz, gpad, uv_dim3, d);
+  if (rc == EMI_SUCCESS && P.lam && f.nuv > 0) {
+    // PMEANU / PMEANV travel with the arrays, or are host arrays beside device-resident fields (a Fortran caller's small dummies): each is
+    // staged where it is in host memory.  The direct transform fills them on the task that owns m = 0 and leaves them alone elsewhere.
+    const bool hu = host || emi_ptr_space(c.meanu) == EMI_MEM_HOST, hv = host || emi_ptr_space(c.meanv) == EMI_MEM_HOST;
+    d.meanu = inverse ? (void *)hs.in(c.meanu, f.nuv, hu, st) : hs.out(c.meanu, f.nuv, hu, true, st);
+    d.meanv = inverse ? (void *)hs.in(c.meanv, f.nuv, hv, st) : hs.out(c.meanv, f.nuv, hv, true, st);
+    if (hs.failed) rc = EMI_ERR_RUNTIME;
+  }
   if (rc == EMI_SUCCESS) {
     std::vector<GridRef> gl;
     grid_fields(f, d, uv_dim3, gl);
+    if (P.lam)  // plane geometry: no 1 / (a cos) on u, v and the N-S derivatives, one factor i m EXWN on every E-W derivative
+      for (GridRef &r : gl) r.g.mode = r.g.mode == GM_ACOS ? GM_PLAIN : (r.g.mode == GM_EWDER_UV ? GM_EWDER : r.g.mode);
     rc = inverse ? inv_pipeline(P, d, f, gl, nproma, adj) : dir_pipeline(P, d, f, gl, nproma, adj);
   }
   if (plan_end(P, st) && rc == EMI_SUCCESS) rc = EMI_ERR_RUNTIME;
   if (rc != EMI_SUCCESS) return rc;
-  if (host) hs.flush(st);
+  if (host || !hs.outs.empty()) hs.flush(st);  // (outputs beside device-resident arrays: the host means of EDIR_TRANS)
 #ifndef EMI_CPU_EMU
   EMI_CHECK(hipGetLastError());
 #endif
@@ -2957,6 +3227,7 @@ static int specnorm_vsets(Plan &P, const double *partial, int nfld, std::vector<
 extern "C" int emi_specnorm(int kresol, int mem_space, const void *spec, int nfld, double *norms) {
   Plan *Pp = get_plan(kresol);
   if (!Pp) EMI_FAIL(EMI_ERR_STATE, "SPECNORM: unknown resolution %d", kresol);
+  if (Pp->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): this routine serves the spherical transforms only", "SPECNORM", kresol);
   // V-sets: a task whose V-set holds none of the fields still takes part in the collective (nfld = 0)
   if (nfld < 0 || (nfld > 0 && (!spec || !norms)) || (nfld == 0 && Pp->nprv == 1)) EMI_FAIL(EMI_ERR_ARG, "SPECNORM: bad arguments");
   if (Pp->nproc > 1 && Pp->nprv == 1 && !G.hc_gather)
@@ -2990,6 +3261,7 @@ extern "C" int emi_specnorm(int kresol, int mem_space, const void *spec, int nfl
 extern "C" int emi_specnorm_kvset(int kresol, int mem_space, const void *spec, int nfld, const int *kvset, int nfld_g, double *norms_g) {
   Plan *Pp = get_plan(kresol);
   if (!Pp) EMI_FAIL(EMI_ERR_STATE, "SPECNORM: unknown resolution %d", kresol);
+  if (Pp->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): this routine serves the spherical transforms only", "SPECNORM", kresol);
   Plan &P = *Pp;
   if (nfld < 0 || nfld_g < 0 || (nfld_g > 0 && (!kvset || !norms_g)) || (nfld > 0 && !spec)) EMI_FAIL(EMI_ERR_ARG, "SPECNORM: bad arguments");
   int mine = 0;
@@ -3029,6 +3301,7 @@ extern "C" int emi_inq_vsets(int *nprtrw, int *nprtrv, int *mysetw, int *mysetv)
 extern "C" int emi_specnorm_partial(int kresol, int mem_space, const void *spec, int nfld, double *sumsq) {
   Plan *Pp = get_plan(kresol);
   if (!Pp) EMI_FAIL(EMI_ERR_STATE, "SPECNORM: unknown resolution %d", kresol);
+  if (Pp->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): this routine serves the spherical transforms only", "SPECNORM", kresol);
   if (!spec || nfld <= 0 || !sumsq) EMI_FAIL(EMI_ERR_ARG, "SPECNORM: bad arguments");
   return specnorm_sumsq(*Pp, mem_space, spec, nfld, sumsq);
 }
@@ -3043,6 +3316,7 @@ extern "C" int emi_gpnorm(int kresol, int mem_space, const void *gp, int gp_nfld
                           int ave_only) {
   Plan *Pp = get_plan(kresol);
   if (!Pp) EMI_FAIL(EMI_ERR_STATE, "GPNORM_TRANS: unknown resolution %d", kresol);
+  if (Pp->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): this routine serves the spherical transforms only", "GPNORM_TRANS", kresol);
   Plan &P = *Pp;
   if (P.ldll) EMI_FAIL(EMI_ERR_UNSUPPORTED, "GPNORM_TRANS: not available on a handle set up with LDLL (it keeps no Gaussian weights)");
   if (kfields <= 0 || !gp || !ave || !pmin || !pmax) EMI_FAIL(EMI_ERR_ARG, "GPNORM_TRANS: bad arguments");
@@ -3185,6 +3459,7 @@ extern "C" int emi_vordiv_to_uv(int ksmax, int precision, int mem_space, const v
 extern "C" int emi_work_model(int kresol, int nfields, double *leg, double *fft, double *fbytes) {
   Plan *Pp = get_plan(kresol);
   if (!Pp) EMI_FAIL(EMI_ERR_STATE, "emi_work_model: unknown resolution %d", kresol);
+  if (Pp->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): this routine serves the spherical transforms only", "emi_work_model", kresol);
   Plan &P = *Pp;
   // LT flops/direction = KF * sum_m 2*NDGLU(m)*(N-m+2)*c_m, c_0=1, c_{m>0}=2 (this
   // task's wavenumbers); FFT ~ 2.5 n log2 n per row; Fourier bytes of this task's latitudes
@@ -3334,6 +3609,7 @@ template <bool SPEC>
 static int dist_impl(int kresol, const void *glob, int nfld, const int *kfrom, const int *ksort, int kproma, void *loc, const char *who) {
   Plan *Pp = get_plan(kresol);
   if (!Pp) EMI_FAIL(EMI_ERR_STATE, "%s: unknown resolution %d", who, kresol);
+  if (Pp->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): this routine serves the spherical transforms only", who, kresol);
   Plan &P = *Pp;
   if (check_tasks(P, kfrom, nfld, who)) return EMI_ERR_ARG;
   if (!loc) EMI_FAIL(EMI_ERR_ARG, "%s: local array missing", who);
@@ -3387,6 +3663,7 @@ template <bool SPEC>
 static int gath_impl(int kresol, void *glob, int nfld, const int *kto, int kproma, const void *loc, const char *who) {
   Plan *Pp = get_plan(kresol);
   if (!Pp) EMI_FAIL(EMI_ERR_STATE, "%s: unknown resolution %d", who, kresol);
+  if (Pp->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): this routine serves the spherical transforms only", who, kresol);
   Plan &P = *Pp;
   if (check_tasks(P, kto, nfld, who)) return EMI_ERR_ARG;
   if (!loc) EMI_FAIL(EMI_ERR_ARG, "%s: local array missing", who);
@@ -3710,10 +3987,14 @@ static int resolve_call(const char *who, const A *ap, A &a) {
                        &a.mem_space, true);
 }
 // INV_TRANS / DIR_TRANSAD run the inverse pipeline, DIR_TRANS / INV_TRANSAD the direct one
-static int transform(int kresol, const Call &c, bool inverse, bool adj) {
-  const char *who = inverse ? (adj ? "DIR_TRANSAD" : "INV_TRANS") : (adj ? "INV_TRANSAD" : "DIR_TRANS");
+static int transform(int kresol, const Call &c, bool inverse, bool adj, bool lam = false) {
+  const char *who = lam ? (inverse ? "EINV_TRANS" : "EDIR_TRANS") : inverse ? (adj ? "DIR_TRANSAD" : "INV_TRANS") : (adj ? "INV_TRANSAD" : "DIR_TRANS");
   Plan *Pp = get_plan(kresol);
   if (!Pp) EMI_FAIL(EMI_ERR_STATE, "%s: unknown resolution %d", who, kresol);
+  if (Pp->lam && !lam)
+    EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): it serves EINV_TRANS and EDIR_TRANS", who, kresol);
+  if (!Pp->lam && lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is not a limited-area handle: it was not set up by ESETUP_TRANS", who, kresol);
+  if (lam && c.vsets) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: KVSET arguments: V-sets are not available on a limited-area handle", who);
   // A handle set up with LDLL holds the inverse panels of its lat-lon rows and nothing else: no Gaussian grid beside them (the
   // reference keeps both on one handle), no Gaussian weights, no panels of the direct transform
   if (Pp->ldll && !(inverse && !adj))
@@ -3734,6 +4015,25 @@ extern "C" int emi_dir_trans(int kresol, const emi_dirtrans_t *args) {
   emi_dirtrans_t a;
   if (resolve_call("DIR_TRANS", args, a)) return EMI_ERR_ARG;
   return transform(kresol, to_call(a), false, false);
+}
+// EINV_TRANS / EDIR_TRANS (etrans/include/etrans/einv_trans.h, edir_trans.h): the argument blocks of INV_TRANS / DIR_TRANS on a handle of
+// ESETUP_TRANS, plus the mean wind PMEANU / PMEANV(nf_uv) -- the (0, 0) coefficients of u and v, which vorticity and divergence do not hold
+extern "C" int emi_einv_trans(int kresol, const emi_invtrans_t *args, const void *meanu, const void *meanv) {
+  EmiRange rg(EMI_LBL_INV);
+  emi_invtrans_t a;
+  if (resolve_call("EINV_TRANS", args, a)) return EMI_ERR_ARG;
+  if (a.ldlatlon) EMI_FAIL(EMI_ERR_UNSUPPORTED, "EINV_TRANS: LDLATLON is not available on a limited-area handle");
+  Call c = to_call(a);
+  c.meanu = (void *)meanu, c.meanv = (void *)meanv;
+  return transform(kresol, c, true, false, true);
+}
+extern "C" int emi_edir_trans(int kresol, const emi_dirtrans_t *args, void *meanu, void *meanv) {
+  EmiRange rg(EMI_LBL_DIR);
+  emi_dirtrans_t a;
+  if (resolve_call("EDIR_TRANS", args, a)) return EMI_ERR_ARG;
+  Call c = to_call(a);
+  c.meanu = meanu, c.meanv = meanv;
+  return transform(kresol, c, false, false, true);
 }
 extern "C" int emi_wait(int kresol) {
   if (!G.init) EMI_FAIL(EMI_ERR_STATE, "emi_wait: SETUP_TRANS0 has not been called");

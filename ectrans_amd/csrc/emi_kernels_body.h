@@ -3248,5 +3248,185 @@ EMI_KERNEL_LB(256) void k_vd2uv(Vd2uvDev d, const real_t *vor, const real_t *div
   pv[isp * d.nfld + f] = v.x * ra, pv[(isp + 1) * d.nfld + f] = v.y * ra;
 }
 
+// ==========================================================================================
+// Limited-area (bi-Fourier) handles: the y-direction transform that stands where the Legendre transform stands on the sphere.
+// Per x-wavenumber m the caller holds, for n = 0 .. KNTMP(m), two complex coefficients a, b (four reals); the y-spectrum is
+//   C_m(n) = a + i b,  C_m(NDGL - n) = conj(a) + i conj(b)  (n >= 1),  zero elsewhere,
+// and F_m(j) = sum_k C_m(k) e^{+2 pi i j k / NDGL} is the x-Fourier coefficient of row j (real part from a, imaginary part from b).
+// One workgroup per (local m, chunk of lam.fbk fields); the complex passes are the generic in-LDS ones of the x-direction
+// (run_dit / blue_conv on the plan T.plans[lam.yplan]: mixed radix 2, 3, 4, 5, 7, 8 where NDGL factorises, Bluestein otherwise).
+// The work array is [field][point] with lam.fs complex numbers between fields: fs is odd, so the loader and the epilogue, which
+// walk it fields-fastest (as the caller's spectral arrays and the Fourier buffer are laid out), hit a different bank group per field
+// while FPAD keeps swizzling the points of one field for the passes.
+// ==========================================================================================
+// waves per SIMD: the fp64 kernels fit the 128 registers of four waves without scratch; the fp32 ones need 13 more, and with
+// several fields per workgroup it is the LDS (up to 80 KiB a workgroup) that bounds the occupancy before the registers do
+#define EMI_LAM_WAVES (sizeof(real_t) == 4 ? 3 : 4)
+EMI_DEVFN void lam_get(const void *av, int sa, int ia, long long isp, int n, real2 &a, real2 &b) {
+  const real_t *p = (const real_t *)av + isp * sa + ia;
+  // the imaginary parts of n = 0 do not enter (the y-transform of the reference is a c2r one)
+  a = mk2(p[0], n == 0 ? (real_t)0.0 : p[sa]);
+  b = mk2(p[2 * (long long)sa], n == 0 ? (real_t)0.0 : p[3 * (long long)sa]);
+}
+
+// k_lam_inv: EPRFI1B + EVDTUV (evdtuv_mod.F90:95-132) + ESPNSDE + ELEINV + EASRE1B.
+//   d/dx = i m EXWN acts on F = A + i B:  a' = -kx b, b' = kx a;   d/dy = i n EYWN acts on a and on b;
+//   u = lap^-1 (d/dx div - d/dy vor),  v = lap^-1 (d/dx vor + d/dy div),  lap = -(kx^2 + ky^2); the (0, 0) coefficient from the means
+EMI_KERNEL_LAM(EMI_LAM_WAVES) void k_lam_inv(EmiGeomDev g, LamDev lam, FftTabDev T, const SpecSrc *flds, int nfld, const real_t *meanu,
+                              const real_t *meanv, real_t *FB, int ldf, int nchunk) {
+  EMI_LDS_DECL;
+  real2 *a = (real2 *)EMI_LDS_PTR;
+  const int ml = EMI_BID / nchunk, f0 = (EMI_BID - ml * nchunk) * lam.fbk;
+  const int nfl = (nfld - f0) < lam.fbk ? (nfld - f0) : lam.fbk;
+  const FftPlanDev &pl = T.plans[lam.yplan];
+  const int L = lam.ndgl, S = pl.S, fs = lam.fs, blue = pl.blue;
+  const int m = g.mval[ml], nm = lam.kntmp[ml];
+  const unsigned short *perm = T.perm + pl.perm_off;
+  const real2 *chirp = (const real2 *)T.chirp + pl.chirp_off;
+  const real_t kx = (real_t)(lam.exwn * (double)m);
+  // ---- loader: the coefficients n = 0 .. nm of every field, fields fastest (the caller's arrays are PSPEC(field, nspec2))
+  for (int idx = EMI_TID; idx < (nm + 1) * nfl; idx += EMI_NTHREADS) {
+    const int n = idx / nfl, fl = idx - n * nfl;
+    const SpecSrc s = flds[f0 + fl];
+    const long long isp = lam.nesm0[ml] + 4LL * n;
+    const real_t ky = (real_t)(lam.eywn * (double)n);
+    real2 ca, cb;
+    if (s.kind == SPK_COPY) {
+      lam_get(s.a, s.sa, s.ia, isp, n, ca, cb);
+    } else if (s.kind == SPK_NSD) {
+      real2 xa, xb;
+      lam_get(s.a, s.sa, s.ia, isp, n, xa, xb);
+      ca = mk2(-ky * xa.y, ky * xa.x), cb = mk2(-ky * xb.y, ky * xb.x);
+    } else {  // SPK_U, SPK_V: s.a = vorticity, s.b = divergence
+      real2 va, vb, da, db;
+      lam_get(s.a, s.sa, s.ia, isp, n, va, vb);
+      lam_get(s.b, s.sb, s.ib, isp, n, da, db);
+      if (m == 0 && n == 0) {
+        const real_t *mean = s.kind == SPK_U ? meanu : meanv;
+        ca = mk2(mean ? mean[s.ia] : (real_t)0.0, (real_t)0.0), cb = mk2((real_t)0.0, (real_t)0.0);
+      } else {
+        const real_t il = (real_t)-1.0 / (kx * kx + ky * ky);
+        if (s.kind == SPK_U) {
+          ca = mk2(il * (-kx * db.x + ky * va.y), il * (-kx * db.y - ky * va.x));
+          cb = mk2(il * (kx * da.x + ky * vb.y), il * (kx * da.y - ky * vb.x));
+        } else {
+          ca = mk2(il * (-kx * vb.x - ky * da.y), il * (-kx * vb.y + ky * da.x));
+          cb = mk2(il * (kx * va.x - ky * db.y), il * (kx * va.y + ky * db.x));
+        }
+      }
+    }
+    real2 *af = a + (long long)fl * fs;
+    const real2 cp = mk2(ca.x - cb.y, ca.y + cb.x);  // a + i b
+    af[FPAD(blue ? n : (int)perm[n])] = blue ? cmulc(cp, chirp[n]) : cp;
+    if (n > 0) {
+      const int k = L - n;
+      const real2 cm = mk2(ca.x + cb.y, cb.x - ca.y);  // conj(a) + i conj(b)
+      af[FPAD(blue ? k : (int)perm[k])] = blue ? cmulc(cm, chirp[k]) : cm;
+    }
+  }
+  // ... and zeros between the two ends of the spectrum (2 KSMAX < NDGL: the ends do not meet)
+  const int nz = L - 2 * nm - 1;
+  for (int idx = EMI_TID; idx < nz * nfl; idx += EMI_NTHREADS) {
+    const int kk = idx / nfl, fl = idx - kk * nfl, k = nm + 1 + kk;
+    a[(long long)fl * fs + FPAD(blue ? k : (int)perm[k])] = mk2((real_t)0.0, (real_t)0.0);
+  }
+  EMI_SYNC();
+  if (blue)
+    blue_conv(a, nfl, fs, pl, T, 1, L, 0);
+  else
+    run_dit(a, nfl, fs, S, pl, T, 0, pl.nfac, 1, +1);
+  // ---- epilogue: F_m(j) of every row to the Fourier buffer, fields fastest; the imaginary part of m = 0 does not exist
+  const real_t invL = blue ? (real_t)(1.0 / (double)S) : (real_t)1.0;
+  for (int idx = EMI_TID; idx < L * nfl; idx += EMI_NTHREADS) {
+    const int j = idx / nfl, fl = idx - j * nfl;
+    real2 z = a[(long long)fl * fs + FPAD(j)];
+    if (blue) z = cscale(cmulc(z, chirp[j]), invL);
+    if (m == 0) z.y = (real_t)0.0;
+    *(real2 *)(FB + (unsigned long long)(unsigned)(lam.rowbase[j] + ml) * (unsigned)ldf + 2 * (f0 + fl)) = z;
+  }
+}
+
+// k_lam_dir: EPRFI2B + ELEDIR + EUVTVD (euvtvd_mod.F90) + EUPDSP.  Z = DFT_NDGL(A + i B) per (m, field); a(n) = (Z(n) + conj Z(-n)) / 2,
+// b(n) = (Z(n) - conj Z(-n)) / 2i; vor = d/dx v - d/dy u, div = d/dx u + d/dy v; the (0, 0) coefficients of u, v to the mean-wind outputs.
+// outs: the spectral outputs of the batch, ascending in src0 (the position of the scalar / of u in the batch; v follows u, so an even
+// lam.fbk keeps the pair in one workgroup).  The 1 / (NDLON NDGL) came with the x-direction kernels (their per-row weight).
+EMI_DEVFN void lam_ab(const real2 *af, int n, int L, int blue, const real2 *chirp, real_t invL, real2 &ca, real2 &cb) {
+  const int k2 = n == 0 ? 0 : L - n;
+  real2 zp = af[FPAD(n)], zm = af[FPAD(k2)];
+  if (blue) zp = cscale(cmul(zp, chirp[n]), invL), zm = cscale(cmul(zm, chirp[k2]), invL);
+  const real2 s = cadd(zp, cconj(zm)), d = csub(zp, cconj(zm));
+  ca = mk2((real_t)0.5 * s.x, (real_t)0.5 * s.y);
+  cb = mk2((real_t)0.5 * d.y, (real_t)-0.5 * d.x);
+}
+EMI_KERNEL_LAM(EMI_LAM_WAVES) void k_lam_dir(EmiGeomDev g, LamDev lam, FftTabDev T, const SpecDst *outs, int nout, int nfld, real_t *meanu,
+                              real_t *meanv, const real_t *FB, int ldf, int nchunk) {
+  EMI_LDS_DECL;
+  real2 *a = (real2 *)EMI_LDS_PTR;
+  const int ml = EMI_BID / nchunk, f0 = (EMI_BID - ml * nchunk) * lam.fbk;
+  const int nfl = (nfld - f0) < lam.fbk ? (nfld - f0) : lam.fbk;
+  const FftPlanDev &pl = T.plans[lam.yplan];
+  const int L = lam.ndgl, S = pl.S, fs = lam.fs, blue = pl.blue;
+  const int m = g.mval[ml], nm = lam.kntmp[ml];
+  const unsigned short *perm = T.perm + pl.perm_off;
+  const real2 *chirp = (const real2 *)T.chirp + pl.chirp_off;
+  for (int idx = EMI_TID; idx < L * nfl; idx += EMI_NTHREADS) {
+    const int j = idx / nfl, fl = idx - j * nfl;
+    const real2 z = *(const real2 *)(FB + (unsigned long long)(unsigned)(lam.rowbase[j] + ml) * (unsigned)ldf + 2 * (f0 + fl));
+    a[(long long)fl * fs + FPAD(blue ? j : (int)perm[j])] = blue ? cmul(z, chirp[j]) : z;
+  }
+  EMI_SYNC();
+  if (blue)
+    blue_conv(a, nfl, fs, pl, T, 0, L, 0);
+  else
+    run_dit(a, nfl, fs, S, pl, T, 0, pl.nfac, 1, -1);
+  // the outputs whose source fields this workgroup holds: [o0, o1)
+  int o0 = 0, o1 = 0;
+  {
+    int lo = 0, hi = nout;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (outs[mid].src0 < f0) lo = mid + 1; else hi = mid;
+    }
+    o0 = lo, hi = nout;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (outs[mid].src0 < f0 + nfl) lo = mid + 1; else hi = mid;
+    }
+    o1 = lo;
+  }
+  const int no = o1 - o0;
+  const real_t invL = blue ? (real_t)(1.0 / (double)S) : (real_t)1.0;
+  const real_t kx = (real_t)(lam.exwn * (double)m);
+  for (int idx = EMI_TID; idx < (nm + 1) * no; idx += EMI_NTHREADS) {
+    const int n = idx / no, oo = idx - n * no;
+    const SpecDst d = outs[o0 + oo];
+    const real_t ky = (real_t)(lam.eywn * (double)n);
+    real2 ca, cb;
+    lam_ab(a + (long long)(d.src0 - f0) * fs, n, L, blue, chirp, invL, ca, cb);
+    if (d.kind != SPO_COPY) {  // SPO_VOR, SPO_DIV: src0 = u, src1 = v
+      real2 wa, wb;
+      lam_ab(a + (long long)(d.src1 - f0) * fs, n, L, blue, chirp, invL, wa, wb);
+      if (d.kind == SPO_VOR) {
+        if (m == 0 && n == 0) {
+          if (meanu) meanu[d.idx] = ca.x;
+          if (meanv) meanv[d.idx] = wa.x;
+        }
+        const real2 ua = ca, ub = cb;
+        ca = mk2(-kx * wb.x + ky * ua.y, -kx * wb.y - ky * ua.x);
+        cb = mk2(kx * wa.x + ky * ub.y, kx * wa.y - ky * ub.x);
+      } else {
+        const real2 ua = ca, ub = cb;
+        ca = mk2(-kx * ub.x - ky * wa.y, -kx * ub.y + ky * wa.x);
+        cb = mk2(kx * ua.x - ky * wb.y, kx * ua.y + ky * wb.x);
+      }
+    }
+    // the entries that do not enter the inverse transform are written as zeros
+    if (n == 0) ca.y = (real_t)0.0, cb.y = (real_t)0.0;
+    if (m == 0) cb = mk2((real_t)0.0, (real_t)0.0);
+    real_t *p = (real_t *)d.dst + (lam.nesm0[ml] + 4LL * n) * d.stride + d.idx;
+    p[0] = ca.x, p[d.stride] = ca.y, p[2 * (long long)d.stride] = cb.x, p[3 * (long long)d.stride] = cb.y;
+  }
+}
+
 #undef FROW
 #undef emi_mfma_f64_16x16x4

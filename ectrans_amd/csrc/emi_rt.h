@@ -27,6 +27,8 @@
 // direct mixed-radix FFT kernels: workgroups of 128 - 256 threads (mr_choose)
 #define EMI_KERNEL_MR(W) __global__ __attribute__((amdgpu_flat_work_group_size(64, 256), amdgpu_waves_per_eu(W, W)))
 #define EMI_KERNEL_LB2(T, W) __global__ __attribute__((amdgpu_flat_work_group_size(T, T), amdgpu_waves_per_eu(W, W)))
+// y-direction kernels of the limited-area handles: workgroups of 256 or 512 threads (1024 would pin the register budget to four waves per SIMD)
+#define EMI_KERNEL_LAM(W) __global__ __attribute__((amdgpu_flat_work_group_size(64, 512), amdgpu_waves_per_eu(W, W)))
 #define EMI_DEVFN __device__ __forceinline__
 #define EMI_TID ((int)threadIdx.x)
 #define EMI_BID ((int)blockIdx.x)
@@ -154,6 +156,7 @@ typedef hipStream_t emi_stream_t;
 #define EMI_KERNEL_LB(T)
 #define EMI_KERNEL_FFT(W)
 #define EMI_KERNEL_LB2(T, W)
+#define EMI_KERNEL_LAM(W)
 #define EMI_KERNEL_MR(W)
 #define EMI_DEVFN inline
 struct EmuCtx {

@@ -79,6 +79,16 @@ struct FuseDst {  // k_leg_dir epilogue: where the coefficients of one W field g
   void *dst;      // real_t array; element (ispec) of the field = dst[ispec * stride + idx]
   int stride, idx;
 };
+// Limited-area (bi-Fourier) handle: what the y-direction kernels k_lam_inv / k_lam_dir need beside EmiGeomDev's nump / mval.  A struct of
+// its own: EmiGeomDev is an argument of every kernel of the spherical path and keeps its layout.
+struct LamDev {
+  int ndgl, yplan;     // rows (extension zone included); index of the complex plan of length NDGL in FftTabDev::plans
+  int fbk, fs;         // fields per workgroup (even); LDS elements (complex) between two fields of its work array (odd: see k_lam_inv)
+  double exwn, eywn;   // wavenumber units of x and y
+  const int *kntmp;    // [nump] largest y-wavenumber of local x-wavenumber ml (the ellipse, ellips.F90)
+  const int *nesm0;    // [nump] 0-based start of its block of 4 (KNTMP + 1) reals in the caller's spectral dimension
+  const int *rowbase;  // [ndgl] row of (row j, local wavenumber 0) in the y-side Fourier buffer: (j, ml) is row rowbase[j] + ml
+};
 enum { GM_PLAIN = 0, GM_ACOS = 1, GM_EWDER = 2, GM_EWDER_UV = 3 };
 struct GridFld {  // one Fourier-space field <-> one user grid field
   void *base;     // real_t array base; element (p) = base[((p/nproma)*nf_arr + fidx)*nproma + p%nproma]

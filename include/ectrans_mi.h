@@ -235,6 +235,35 @@ int emi_dir_trans(int kresol, const emi_dirtrans_t *args);
 int emi_inv_transad(int kresol, const emi_invtrans_t *args);
 int emi_dir_transad(int kresol, const emi_dirtrans_t *args);
 
+/* ---- ESETUP_TRANS / EINV_TRANS / EDIR_TRANS (etrans/include/etrans/esetup_trans.h, einv_trans.h, edir_trans.h) -------------------
+ * The limited-area, bi-Fourier transforms of AROME / HARMONIE-AROME / ALARO: a plane grid of KDGL rows (extension zone included) of
+ * one row length NDLON, a spectrum truncated to the ellipse (m / KMSMAX)^2 + (n / KSMAX)^2 <= 1 (ellips.F90).  Handles share the
+ * numbering of emi_setup; emi_inq_int(kresol, "ldlam") tells them apart.  INTEGRATION.md ("Limited-area transforms") defines the
+ * transform; in short, per x-wavenumber m and n = 0 .. KNTMP(m) the spectral arrays hold four reals (a_r, a_i, b_r, b_i) with the field
+ * index fastest, PSPEC(nfld, nspec2), and grid arrays hold the rows one after the other.
+ * A limited-area handle serves emi_einv_trans, emi_edir_trans, the inquiries, emi_wait and emi_release; every spherical routine
+ * returns EMI_ERR_UNSUPPORTED on it, and the two E-transforms return it on a handle of emi_setup.  NPRTRV > 1 is refused.
+ * Further inquiries of such a handle -- emi_inq_int: "ldlam" "nmsmax" ("nsmax" is KSMAX) "ndgux"; emi_inq_int_array, all over
+ * m = 0 .. KMSMAX unless stated: "kntmp" "ncpl2m" "ncpl4m" "npme" "nesm0" (1-based, -99 for the wavenumbers of other tasks)
+ * "ndim0g" "nallms" "numpp"(nprtrw) "nptrms"(nprtrw) "npossp"(nprtrw + 1); emi_inq_real_array: "rlepinm"(nspec2g / 4).            */
+typedef struct {
+  int kmsmax, ksmax; /* KMSMAX, KSMAX: truncation in x and in y; both below half the row / column length      */
+  int kdgl;          /* KDGL rows                                                                              */
+  const int *kloen;  /* KLOEN(kdgl), every entry the same row length; NULL: kdlon                             */
+  int kdlon;
+  int kdgux;         /* KDGUX, last row of the computational + intermediate zone: kept for inquiry            */
+  double pexwn, peywn; /* PEXWN, PEYWN: wavenumber units, 2 pi / (NDLON dx) and 2 pi / (KDGL dy)                */
+  int precision;     /* as emi_setup_t                                                                         */
+} emi_esetup_t;
+int emi_esetup(const emi_esetup_t *cfg, int *kresol);
+/* The argument blocks of emi_inv_trans / emi_dir_trans (ldlatlon and vsets must be unset) and the mean wind PMEANU / PMEANV: nf_uv
+ * reals of the handle's precision, in the memory the other arrays live in -- the (0, 0) coefficients of u and v, read by the inverse
+ * (NULL: zero) and written by the direct transform (NULL: dropped; with several tasks the task that owns m = 0 writes them).  Host
+ * means beside device-resident fields are accepted too (what the Fortran shim passes): the direct transform then returns once they
+ * are there.                                                                                                                       */
+int emi_einv_trans(int kresol, const emi_invtrans_t *args, const void *meanu, const void *meanv);
+int emi_edir_trans(int kresol, const emi_dirtrans_t *args, void *meanu, void *meanv);
+
 /* ---- SPECNORM (trans/include/ectrans/specnorm.h:12) --------------------------------- */
 int emi_specnorm(int kresol, int mem_space, const void *spec, int nfld, double *norms /* host */);
 

@@ -1,0 +1,314 @@
+"""ESETUP_TRANS / EINV_TRANS / EDIR_TRANS / ETRANS_INQ -- the limited-area bi-Fourier transforms -- on the CPU functional emulator
+(tests/emu): the same host logic and kernels as the GPU tier (tests/test_lam_gpu.py), against the NumPy model of tests/lam_ref.py.
+The model is first pinned to the reference's own known-answer pair (tests/golden/antwrp1300, from its ectrans4py test data)."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from tests.lam_common import lam_case, units
+from tests.lam_ref import LamRef, ellips, zigzag
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden", "antwrp1300")
+EPSILON = 1e-10  # absolute: the bound of the reference's own test of this pair
+TOL = 1e-12      # fp64, of each field's maximum (the emulator tier's bound, tests/test_emu_parity.py)
+TOL32 = 3e-5     # the project's fp32 bound
+G_NDLON, G_NDGL, G_M, G_N = 54, 48, 26, 23  # the golden pair: 54 x 48 points, truncation 26 x 23, 1300 m
+
+
+def golden():
+    return np.load(os.path.join(GOLD, "antwrp1300-s1t@sp.npy")), np.load(os.path.join(GOLD, "antwrp1300-s1t@sp2gp.npy"))
+
+
+@pytest.fixture(scope="module")
+def et():
+    os.environ.setdefault("OMP_NUM_THREADS", "256")
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "emu")])
+    import ectrans_amd
+    ectrans_amd._use_library_for_tests(os.path.join(ROOT, "tests", "emu", "libectrans_mi_emu.so"))
+    ectrans_amd.setup_trans0(kmax_resol=4)
+    yield ectrans_amd
+    ectrans_amd.trans_end()
+    ectrans_amd._L = None
+
+
+# ---- 1. the model, pinned to the golden pair ---------------------------------------------------------------------------------------
+def test_model_matches_golden_pair():
+    sp, gp = golden()
+    ref = LamRef(G_NDLON, G_NDGL, G_M, G_N, *units(G_NDLON, G_NDGL))
+    assert (ref.ngptot, ref.nspec2) == (2592, 1968) == (gp.size, sp.size)
+    g = ref.inv_trans(spsc=sp[:, None])[0]
+    s = ref.dir_trans(gp[None], nsc=1)[2][:, 0]
+    print("model vs golden: inverse %.2e direct %.2e (data up to %.0f)" % (np.abs(g - gp).max(), np.abs(s - sp).max(), np.abs(gp).max()))
+    assert np.abs(g - gp).max() < EPSILON
+    assert np.abs(s - sp).max() < EPSILON
+    assert np.array_equal(ref.clean(sp[:, None])[:, 0], sp)  # the golden spectrum holds zeros in the entries that do not enter
+
+
+# ---- 2. the golden pair through the library ----------------------------------------------------------------------------------------
+def test_library_matches_golden_pair(et):
+    sp, gp = golden()
+    exwn, eywn = units(G_NDLON, G_NDGL)
+    r = et.esetup_trans(G_M, G_N, G_NDGL, kdgux=37, kloen=np.full(G_NDGL, G_NDLON), pexwn=exwn, peywn=eywn)
+    assert (et.etrans_inq(r, "ngptot"), et.etrans_inq(r, "nspec2")) == (2592, 1968)
+    out = np.zeros((1, 1, 2592))
+    et.einv_trans(r, pspscalar=np.ascontiguousarray(sp[:, None]), pgp=out)
+    s = np.zeros((1968, 1))
+    et.edir_trans(r, pspscalar=s, pgp=np.ascontiguousarray(gp.reshape(1, 1, -1)))
+    et.trans_release(r)
+    print("library vs golden: inverse %.2e direct %.2e" % (np.abs(out[0, 0] - gp.ravel()).max(), np.abs(s[:, 0] - sp).max()))
+    assert np.abs(out[0, 0] - gp.ravel()).max() < EPSILON
+    assert np.abs(s[:, 0] - sp).max() < EPSILON
+
+
+# ---- 3. parity with the model -------------------------------------------------------------------------------------------------------
+# (ndlon, ndgl, M, N, keywords of lam_case).  Row and column lengths: even, odd, with a factor 7 or 11, prime (11 and the primes take
+# the Bluestein plans); all four derivative / wind flags and a non-zero mean wind in every case.
+CASES = {
+    "golden_size": (54, 48, 26, 23, {}),
+    "split_arrays_nproma": (54, 48, 26, 23, dict(split=True, nproma=100)),       # PGPUV / PGP2 / PGP3A / PGP3B, NPROMA cuts rows
+    "odd_x_prime_y": (45, 37, 14, 12, dict(nproma=77)),                          # NDGL = 37: Bluestein; NPROMA does not divide 1665
+    "prime_x_factor7_y": (53, 42, 17, 13, {}),                                   # NDLON = 53: Bluestein in x; NDGL = 2 3 7
+    "factor11_both": (44, 33, 14, 10, dict(split=True)),                         # 44 = 4 11, 33 = 3 11
+    "factor7_x_odd_y": (56, 45, 18, 14, {}),                                     # quadratic truncation: M = 56 / 3, N = 45 / 3 - 1
+    "linear_m_ne_n": (64, 30, 31, 14, {}),                                       # linear truncation, M /= N
+    "m_zero": (22, 26, 0, 5, {}),
+    "n_zero": (22, 26, 7, 0, {}),
+    "device_arrays": (40, 35, 19, 17, dict(mem_space=1)),                        # EMI_MEM_DEVICE: arrays used in place
+    "device_arrays_split": (40, 36, 13, 17, dict(mem_space=1, split=True, nproma=64)),
+    "no_flags": (36, 32, 11, 15, dict(flags=False)),
+    "scalars_only": (36, 32, 11, 15, dict(nuv=0)),
+    "two_rows": (16, 2, 5, 0, {}),                                               # the shortest column the interface takes
+}
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_parity_fp64(et, name):
+    ndlon, ndgl, M, N, kw = CASES[name]
+    errs, _ = lam_case(et, ndlon, ndgl, M, N, **kw)
+    print(name, {k: "%.1e" % v for k, v in errs.items()})
+    assert max(errs.values()) < TOL, errs
+
+
+@pytest.mark.parametrize("name", ["golden_size", "split_arrays_nproma", "odd_x_prime_y", "prime_x_factor7_y", "factor11_both", "m_zero", "n_zero"])
+def test_parity_fp32(et, name):
+    ndlon, ndgl, M, N, kw = CASES[name]
+    errs, _ = lam_case(et, ndlon, ndgl, M, N, precision=4, **kw)
+    print(name, {k: "%.1e" % v for k, v in errs.items()})
+    assert max(errs.values()) < TOL32, errs
+    assert max(errs.values()) > 1e-9  # really computed in float
+
+
+def test_several_batches(et):
+    """a field count above the batch limit: the calls run in several batches, u and v of a pair and the derivative fields in whichever
+    batch the limit puts them"""
+    et.set_max_batch(64)
+    try:
+        errs, _ = lam_case(et, 24, 20, 7, 6, nuv=30, nsc=40)  # 4 x 30 + 2 x 40 inverse fields + 60 Fourier-space derivatives; 100 direct
+    finally:
+        et.set_max_batch(0)
+    assert max(errs.values()) < TOL, errs
+
+
+# ---- 4. round trips -----------------------------------------------------------------------------------------------------------------
+def test_round_trips(et):
+    ndlon, ndgl, M, N = 48, 40, 15, 13
+    exwn, eywn = units(ndlon, ndgl)
+    ref = LamRef(ndlon, ndgl, M, N, exwn, eywn)
+    r = et.esetup_trans(M, N, ndgl, kdlon=ndlon, pexwn=exwn, peywn=eywn)
+    rng = np.random.default_rng(11)
+    vor, div, sc = ref.random_spec(rng, 2), ref.random_spec(rng, 2), ref.random_spec(rng, 3)
+    vor[0], div[0] = 0.0, 0.0  # the (0, 0) coefficients of vorticity and divergence are not recoverable from the wind
+    mu, mv = np.array([1.25, -0.5]), np.array([0.75, 2.0])
+    gp = np.zeros((1, 7, ref.ngptot))
+    et.einv_trans(r, pspvor=vor, pspdiv=div, pspscalar=sc, pmeanu=mu, pmeanv=mv, pgp=gp)
+    v2, d2, s2, mu2, mv2 = np.zeros_like(vor), np.zeros_like(div), np.zeros_like(sc), np.zeros(2), np.zeros(2)
+    et.edir_trans(r, pspvor=v2, pspdiv=d2, pspscalar=s2, pmeanu=mu2, pmeanv=mv2, pgp=gp)
+    # inverse then direct returns the spectrum and the means
+    for a, b in ((v2, vor), (d2, div), (s2, sc)):
+        assert np.abs(a - b).max() < TOL * np.abs(b).max()
+    assert np.abs(mu2 - mu).max() < TOL * np.abs(gp).max() and np.abs(mv2 - mv).max() < TOL * np.abs(gp).max()
+    # direct then inverse returns a band-limited field
+    gp2 = np.zeros_like(gp)
+    et.einv_trans(r, pspvor=v2, pspdiv=d2, pspscalar=s2, pmeanu=mu2, pmeanv=mv2, pgp=gp2)
+    for f in range(7):
+        assert np.abs(gp2[0, f] - gp[0, f]).max() < TOL * np.abs(gp[0, f]).max()
+    et.trans_release(r)
+
+
+def test_wait_and_release(et):
+    """emi_wait accepts the handle; a released slot is reused (the phase timers are HIP events: tests/test_lam_gpu.py checks their slots)"""
+    r = et.esetup_trans(7, 6, 20, kdlon=24, pexwn=1.0, peywn=1.0)
+    sc, gp = np.zeros((et.etrans_inq(r, "nspec2"), 1)), np.zeros((1, 1, 480))
+    et.einv_trans(r, pspscalar=sc, pgp=gp)
+    assert et.lib().emi_wait(r) == 0
+    et.trans_release(r)
+    assert et.esetup_trans(7, 6, 20, kdlon=24, pexwn=1.0, peywn=1.0) == r
+    et.trans_release(r)
+    with pytest.raises(et.TransError, match="unknown resolution"):
+        et.etrans_inq(r, "nspec2")
+
+
+# ---- 5. inquiries ---------------------------------------------------------------------------------------------------------------------
+def test_inquiries_one_task(et):
+    ndlon, ndgl, M, N = 54, 48, 26, 23
+    exwn, eywn = units(ndlon, ndgl)
+    r = et.esetup_trans(M, N, ndgl, kdgux=37, kdlon=ndlon, pexwn=exwn, peywn=eywn)
+    ref = LamRef(ndlon, ndgl, M, N, exwn, eywn)
+    q = lambda n: et.etrans_inq(r, n)
+    kn = ellips(M, N)
+    assert q("ldlam") == 1 and q("nsmax") == N and q("nmsmax") == M and q("ndgl") == ndgl and q("ndlon") == ndlon and q("ndgux") == 37
+    assert q("nspec2") == q("nspec2g") == q("nspec2mx") == q("nspec") == ref.nspec2 == 1968
+    assert q("ngptot") == q("ngptotg") == q("ngptotmx") == 2592 and q("nump") == M + 1
+    assert np.array_equal(q("kntmp"), kn) and np.array_equal(q("ncpl2m"), 2 * (kn + 1)) and np.array_equal(q("ncpl4m"), 4 * (kn + 1))
+    assert np.array_equal(q("nesm0"), [ref.nesm0[m] for m in range(M + 1)]) and np.array_equal(q("ndim0g"), q("nesm0"))
+    assert np.array_equal(q("npme"), 1 + np.concatenate([[0], np.cumsum(kn[:-1] + 1)]))
+    assert np.array_equal(q("myms"), np.arange(M + 1)) and np.array_equal(q("nallms"), np.arange(M + 1))
+    assert list(q("numpp")) == [M + 1] and list(q("nptrms")) == [1] and list(q("npossp")) == [1, 1969] and list(q("latlo")) == [0, ndgl]
+    lep = q("rlepinm")
+    want = []
+    for m in range(M + 1):
+        for n in range(kn[m] + 1):
+            lap = -((m * exwn) ** 2 + (n * eywn) ** 2)
+            want.append(1.0 / lap if lap else 0.0)
+    assert np.allclose(lep, want, rtol=1e-15, atol=0.0)
+    assert et.trans_inq(r, "nspec2") == 1968  # the scalar inquiries of TRANS_INQ answer on either kind of handle
+    et.trans_release(r)
+
+
+# ---- 6. refusals ------------------------------------------------------------------------------------------------------------------------
+def test_refusals_of_the_e_routines(et):
+    T = et.TransError
+    ok = dict(kdlon=24, pexwn=1.0, peywn=1.0)
+    kl = np.full(20, 24)
+    kl[7] = 20
+    with pytest.raises(T, match="ESETUP_TRANS: KLOEN MUST HOLD ONE ROW LENGTH"):
+        et.esetup_trans(7, 6, 20, kloen=kl, pexwn=1.0, peywn=1.0)
+    with pytest.raises(T, match="ESETUP_TRANS: KNOEXTZL"):
+        et.esetup_trans(7, 6, 20, knoextzl=2, **ok)
+    with pytest.raises(T, match="ESETUP_TRANS: KNOEXTZL / KNOEXTZG"):
+        et.esetup_trans(7, 6, 20, knoextzg=2, **ok)
+    with pytest.raises(T, match="ESETUP_TRANS: PWEIGHT"):
+        et.esetup_trans(7, 6, 20, pweight=np.ones(20), **ok)
+    with pytest.raises(T, match="ESETUP_TRANS: LDGRIDONLY"):
+        et.esetup_trans(7, 6, 20, ldgridonly=True, **ok)
+    with pytest.raises(T, match="ESETUP_TRANS: KTMAX"):
+        et.esetup_trans(7, 6, 20, ktmax=5, **ok)
+    with pytest.raises(T, match="ESETUP_TRANS: KMSMAX = 12 MUST BE BELOW HALF THE ROW LENGTH 24"):
+        et.esetup_trans(12, 6, 20, **ok)
+    with pytest.raises(T, match="ESETUP_TRANS: KSMAX = 10 MUST BE BELOW HALF OF KDGL = 20"):
+        et.esetup_trans(7, 10, 20, **ok)
+    with pytest.raises(T, match="ESETUP_TRANS: KDGL = 6007 NEEDS A WORK ARRAY OF .* AT MOST 5120"):
+        et.esetup_trans(3, 3, 6007, kdlon=8, pexwn=1.0, peywn=1.0)  # a prime column: convolution length 12288
+    r = et.esetup_trans(7, 6, 20, ktmax=6, ldusefftw=True, ld_all_fftw=True, **ok)  # accepted, no effect
+    sc, gp = np.zeros((et.etrans_inq(r, "nspec2"), 1)), np.zeros((1, 1, 480))
+    with pytest.raises(T, match="EINV_TRANS: FSPGL_PROC"):
+        et.einv_trans(r, pspscalar=sc, pgp=gp, fspgl_proc=print)
+    with pytest.raises(T, match="EDIR_TRANS: AUX_PROC"):
+        et.edir_trans(r, pspscalar=sc, pgp=gp, aux_proc=print)
+    et.trans_release(r)
+
+
+def test_spherical_routines_refuse_a_lam_handle(et):
+    T = et.TransError
+    r = et.esetup_trans(7, 6, 20, kdlon=24, pexwn=1.0, peywn=1.0)
+    ns2 = et.etrans_inq(r, "nspec2")
+    sc, gp = np.zeros((ns2, 1)), np.zeros((1, 1, 480))
+    lam = "is a limited-area handle \\(ESETUP_TRANS\\)"
+    for fn, who in ((et.inv_trans, "INV_TRANS"), (et.dir_trans, "DIR_TRANS"), (et.inv_transad, "INV_TRANSAD"), (et.dir_transad, "DIR_TRANSAD")):
+        with pytest.raises(T, match=who + ": resolution %d %s" % (r, lam)):
+            fn(r, pspscalar=sc, pgp=gp)
+    with pytest.raises(T, match="SPECNORM: resolution %d %s" % (r, lam)):
+        et.specnorm(r, sc)
+    with pytest.raises(T, match="GPNORM_TRANS: resolution %d %s" % (r, lam)):
+        et.gpnorm_trans(r, gp)
+    with pytest.raises(T, match="DIST_SPEC: resolution %d %s" % (r, lam)):
+        et.dist_spec(r, np.zeros((ns2, 1)), 1)
+    with pytest.raises(T, match="GATH_SPEC: resolution %d %s" % (r, lam)):
+        et.gath_spec(r, sc, 1)
+    with pytest.raises(T, match="DIST_GRID: resolution %d %s" % (r, lam)):
+        et.dist_grid(r, np.zeros((1, 480)), 1)
+    with pytest.raises(T, match="GATH_GRID: resolution %d %s" % (r, lam)):
+        et.gath_grid(r, gp, 1)
+    for name in ("rmu", "rgw", "nasm0", "ndglu"):
+        with pytest.raises(T, match="TRANS_INQ: %s: resolution %d %s" % (name, r, lam)):
+            et.trans_inq(r, name)
+    with pytest.raises(T, match="emi_inq_legendre: resolution %d %s" % (r, lam)):
+        et.legendre_panel(r, 0, True)
+    et.trans_release(r)
+
+
+def test_e_routines_refuse_a_gaussian_handle(et):
+    T = et.TransError
+    r = et.setup_trans(5, 8)
+    sc, gp = np.zeros((et.trans_inq(r, "nspec2"), 1)), np.zeros((1, 1, et.trans_inq(r, "ngptot")))
+    assert et.lib().emi_inq_int  # (the scalar "ldlam" answers 0 on it)
+    with pytest.raises(T, match="EINV_TRANS: resolution %d is not a limited-area handle" % r):
+        et.einv_trans(r, pspscalar=sc, pgp=gp)
+    with pytest.raises(T, match="EDIR_TRANS: resolution %d is not a limited-area handle" % r):
+        et.edir_trans(r, pspscalar=sc, pgp=gp)
+    with pytest.raises(T, match="ETRANS_INQ: resolution %d is not a limited-area handle" % r):
+        et.etrans_inq(r, "nspec2")
+    et.trans_release(r)
+
+
+# ---- 7. several tasks -------------------------------------------------------------------------------------------------------------------
+def _run_workers(nproc, outdir):
+    env = dict(os.environ, PYTHONPATH=ROOT, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="256")
+    import socket
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        env["MASTER_PORT"] = str(s.getsockname()[1])
+    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "lam_dist_worker.py"), str(rank), str(nproc), outdir], env=env)
+             for rank in range(nproc)]
+    codes = [p.wait(timeout=600) for p in procs]
+    assert codes == [0] * nproc, codes
+    return [np.load(os.path.join(outdir, "lam_%d_of_%d.npz" % (rank, nproc))) for rank in range(nproc)]
+
+
+@pytest.mark.parametrize("nproc", [2, 3])
+def test_tasks_assemble_to_the_one_task_result(nproc, tmp_path):
+    """2 and 3 tasks over gloo on a 60 x 50 grid (wind, scalars, all derivatives, both directions): the per-task pieces, assembled
+    through the inquiry arrays, are byte-identical to the one-task result -- the criterion of tests/test_decomposition_invariance.py"""
+    one = _run_workers(1, str(tmp_path))[0]
+    parts = _run_workers(nproc, str(tmp_path))
+    ndlon, ndgl, M, N = 60, 50, 19, 16
+    kn = ellips(M, N)
+    # the inquiry arrays against a plain restatement of the distribution
+    procm = zigzag(M, nproc)
+    rows = [r * (ndgl // nproc) + min(r, ndgl % nproc) for r in range(nproc + 1)]
+    ndim0g, pos = np.zeros(M + 1, dtype=np.int64), 1
+    for w in range(nproc):
+        for m in np.flatnonzero(procm == w):
+            ndim0g[m] = pos
+            pos += 4 * (kn[m] + 1)
+    grid = np.zeros_like(one["grid"])
+    spec = {k: np.zeros_like(one[k]) for k in ("vor", "div", "sc")}
+    mean = None
+    for w, p in enumerate(parts):
+        myms = np.flatnonzero(procm == w)
+        assert np.array_equal(p["myms"], myms) and np.array_equal(p["procm"], procm + 1) and np.array_equal(p["latlo"], rows)
+        assert np.array_equal(p["ndim0g"], ndim0g) and p["nump"] == len(myms)
+        assert np.array_equal(p["numpp"], [np.sum(procm == k) for k in range(nproc)])
+        assert np.array_equal(p["nptrms"], 1 + np.concatenate([[0], np.cumsum(p["numpp"])[:-1]]))
+        assert np.array_equal(p["nallms"], np.concatenate([np.flatnonzero(procm == k) for k in range(nproc)]))
+        sizes = [4 * int(np.sum(kn[procm == k] + 1)) for k in range(nproc)]
+        assert np.array_equal(p["npossp"], 1 + np.concatenate([[0], np.cumsum(sizes)])) and p["nspec2"] == sizes[w] and p["nspec2mx"] == max(sizes)
+        nesm0 = np.full(M + 1, -99)
+        nesm0[myms] = 1 + np.concatenate([[0], np.cumsum(4 * (kn[myms] + 1))[:-1]])
+        assert np.array_equal(p["nesm0"], nesm0)
+        assert p["ngptot"] == (rows[w + 1] - rows[w]) * ndlon and p["nfrstlat"] == rows[w] + 1 and p["nlstlat"] == rows[w + 1]
+        grid[:, rows[w] * ndlon:rows[w + 1] * ndlon] = p["grid"]
+        for m in myms:  # this task's block of wavenumber m to its place in the one-task layout
+            n4 = 4 * (kn[m] + 1)
+            for k in spec:
+                spec[k][one["nesm0"][m] - 1:one["nesm0"][m] - 1 + n4] = p[k][nesm0[m] - 1:nesm0[m] - 1 + n4]
+        if 0 in myms:
+            mean = p["mean"]
+    assert grid.tobytes() == one["grid"].tobytes()
+    for k in spec:
+        assert spec[k].tobytes() == one[k].tobytes(), k
+    assert mean.tobytes() == one["mean"].tobytes()
