@@ -74,6 +74,12 @@ def main():
     et.dir_trans(r, pspvor=v2, pspdiv=d2, pspscalar=s2, pgp=to(gdir[None, :, gp0:gp0 + ng]))
     vr, dr, sr = o.dir_trans(gdir, nuv=nuv, nsc=nsc)
     e_dir = max(rel_err(back(a), b[gidx]) for a, b in ((v2, vr), (d2, dr), (s2, sr)))
+    # the same leg on full-bandwidth input: the same global white field on every task (energy above NMEN in every row, which the band-limited
+    # field above does not hold), this task's rows in, this task's wavenumbers against the global reference
+    gw = np.random.default_rng(12).uniform(-1.0, 1.0, gdir.shape).astype(DT).astype(np.float64)
+    v3, d3, s3 = to(np.zeros((ns2, nuv))), to(np.zeros((ns2, nuv))), to(np.zeros((ns2, nsc)))
+    et.dir_trans(r, pspvor=v3, pspdiv=d3, pspscalar=s3, pgp=to(gw[None, :, gp0:gp0 + ng]))
+    e_white = max(rel_err(back(a), b[gidx]) for a, b in zip((v3, d3, s3), o.dir_trans(gw, nuv=nuv, nsc=nsc)))
     e_norm = np.abs(et.specnorm(r, to(loc(sc))) / o.specnorm(sc) - 1.0).max()
     # utility routines with several tasks: VORDIV_TO_UV on this task's wavenumbers, GPNORM_TRANS = the global norms on every task
     ur, vr = o.vordiv_to_uv(vor, div)
@@ -83,11 +89,11 @@ def main():
     ar, mnr, mxr = o.gpnorm(gref)
     gsc = np.abs(gref).max(axis=1)
     e_gpn = max((np.abs(ave - ar) / gsc).max(), (np.abs(gmn - mnr) / gsc).max(), (np.abs(gmx - mxr) / gsc).max())
-    print("rank %d/%d: nump %d nlat %d e_inv %.2e e_dir %.2e e_norm %.2e e_uv %.2e e_gpnorm %.2e" % (
-        rank, world, len(myms), lat1 - lat0, e_inv, e_dir, e_norm, e_uv, e_gpn), flush=True)
+    print("rank %d/%d: nump %d nlat %d e_inv %.2e e_dir %.2e e_white %.2e e_norm %.2e e_uv %.2e e_gpnorm %.2e" % (
+        rank, world, len(myms), lat1 - lat0, e_inv, e_dir, e_white, e_norm, e_uv, e_gpn), flush=True)
     assert e_uv < (1e-12 if PREC == 8 else 3e-6) and e_gpn < (1e-12 if PREC == 8 else 3e-5), (e_uv, e_gpn)
     tol = (1e-12, 1e-13) if PREC == 8 else (3e-5, 1e-5)  # fp32 library: as tests/test_gpu_parity.py
-    assert e_inv < tol[0] and e_dir < tol[0] and e_norm < tol[1], (e_inv, e_dir, e_norm)
+    assert e_inv < tol[0] and e_dir < tol[0] and e_white < tol[0] and e_norm < tol[1], (e_inv, e_dir, e_white, e_norm)
     if PREC != 8:  # the re-layout helpers below are precision independent; exact-equality checks in fp64 only
         et.trans_release(r)
         et.trans_end()

@@ -68,9 +68,9 @@ def lam_case(et, ndlon, ndgl, M, N, nuv=2, nsc=3, split=False, nproma=None, prec
     errs = {}
 
     def cmp(label, got, want):
-        for f in range(want.shape[0]):
+        for f in range(want.shape[0]):  # NaN in the output counts as infinite
             e = float(np.abs(got[f] - want[f]).max() / max(np.abs(want[f]).max(), 1e-300))
-            errs[label] = max(errs.get(label, 0.0), e)
+            errs[label] = max(errs.get(label, 0.0), e if np.isfinite(e) else np.inf)
 
     if not split:
         sp_in["pspscalar"] = C(sc)
@@ -84,7 +84,7 @@ def lam_case(et, ndlon, ndgl, M, N, nuv=2, nsc=3, split=False, nproma=None, prec
         if nb * nproma > npt:  # the padding of the last block is not written
             assert np.all(to_host(pgp)[-1, :, npt - (nb - 1) * nproma:] == -777.0)
         gin_h = blocked(np.concatenate(([grp["u"], grp["v"]] if nuv else []) + [grp["sc"]]), nproma, dt)
-        gin_h[gin_h == -777.0] = 0.0
+        gin_h[gin_h == -777.0] = np.nan  # a Fortran caller leaves the padding of the last block uninitialised: it must not be read
         dir_in = dict(pgp=to_dev(gin_h))
         sp_out = dict(pspscalar=Z(ref.nspec2, nsc))
     else:
@@ -109,7 +109,7 @@ def lam_case(et, ndlon, ndgl, M, N, nuv=2, nsc=3, split=False, nproma=None, prec
             cmp("inv2 " + nm, g2[k:k + 1], grp[nm][0:1])
             cmp("inv3a " + nm, g3a[4 * k:4 * k + 4], grp[nm][1:5])
             cmp("inv3b " + nm, g3b[k:k + 1], grp[nm][5:6])
-        z0 = lambda a: np.where(a == -777.0, 0.0, a).astype(dt)
+        z0 = lambda a: np.where(a == -777.0, np.nan, a).astype(dt)  # (NaN padding, as above)
         dir_in = dict(pgp2=to_dev(z0(blocked(grp["sc"][0:1], nproma, dt))),
                       pgp3a=to_dev(z0(blocked(grp["sc"][1:5], nproma, dt).reshape(nb, 2, 2, nproma))),
                       pgp3b=to_dev(z0(blocked(grp["sc"][5:6], nproma, dt).reshape(nb, 1, 1, nproma))))
@@ -134,10 +134,106 @@ def lam_case(et, ndlon, ndgl, M, N, nuv=2, nsc=3, split=False, nproma=None, prec
         cmp("dir vor", outs["vor"].T, rv.T)
         cmp("dir div", outs["div"].T, rd.T)
         scale = max(np.abs(gu[:2 * nuv]).max(), 1e-300)
-        errs["dir mean"] = float(max(np.abs(to_host(sp_out["pmeanu"]) - rmu).max(), np.abs(to_host(sp_out["pmeanv"]) - rmv).max()) / scale)
+        e = float(np.max(np.abs(np.concatenate([to_host(sp_out["pmeanu"]) - rmu, to_host(sp_out["pmeanv"]) - rmv]))) / scale)
+        errs["dir mean"] = e if np.isfinite(e) else np.inf
     # the entries that do not enter the inverse transform are written as exact zeros
     for nm, a in outs.items():
         assert np.array_equal(ref.clean(a), a), "structural zeros of " + nm
     if kresol is None:
         et.trans_release(r)
     return errs, outs
+
+
+def fp32_lam_direct(ref, g):
+    """The float32 yardstick of EDIR_TRANS for one scalar grid field g (ndgl, ndlon): LamRef.analyse restated in single precision --
+    scipy's single-precision real-to-complex FFT of every row, its complex FFT of every column, the split into (a, b), all in
+    float32 / complex64 on float32 data.  Reference arithmetic only, nothing of the library.  Returns (nspec2, 1) in float64."""
+    import scipy.fft
+    L, N, M = ref.ndgl, ref.N, ref.M
+    g32 = np.asarray(g, dtype=np.float32)
+    X = scipy.fft.rfft(g32, axis=1)[:, :M + 1] / np.float32(ref.ndlon)
+    Z = scipy.fft.fft(X, axis=0) / np.float32(L)  # Z[k, m]
+    assert X.dtype == np.complex64 and Z.dtype == np.complex64
+    Zp = Z[:N + 1, :].T
+    Zm = np.conj(Z[(-np.arange(N + 1)) % L, :].T)
+    a, b = np.complex64(0.5) * (Zp + Zm), np.complex64(-0.5j) * (Zp - Zm)
+    assert a.dtype == np.complex64
+    a, b = ref.mask(a[None].astype(np.complex128)), ref.mask(b[None].astype(np.complex128))
+    a[:, :, 0], b[:, :, 0] = a[:, :, 0].real, b[:, :, 0].real
+    b[:, 0, :] = 0.0
+    return ref.pack(a, b)
+
+
+def lam_white_case(et, ndlon, ndgl, M, N, nuv=2, nsc=3, split=False, nproma=None, precision=8, mem_space=None, seed=31, to_dev=None,
+                   to_host=None, kresol=None):
+    """EDIR_TRANS of FULL-BANDWIDTH grid fields against LamRef.dir_trans: U(-1,1) white noise in every point of the (nf, ndgl, ndlon)
+    fields (rounded to the library precision before the model sees it) -- energy above KMSMAX in every row and outside the ellipse, which
+    the transform must discard; the fields of lam_case hold none there.  Winds (vorticity, divergence, PMEANU / PMEANV), scalars, the
+    structural zeros; the single-array and (split) the split-array call forms; the padding of the last NPROMA block is NaN.
+    Returns (errs, yard): errs as lam_case; yard (precision=4 only) = {"lib", "cpu"}: the error of the library and of the float32
+    yardstick fp32_lam_direct on scalar field 0, both against the float64 model, relative to the field's largest coefficient."""
+    dt = np.float64 if precision == 8 else np.float32
+    to_dev = to_dev or (lambda a: a)
+    to_host = to_host or (lambda a: a)
+    exwn, eywn = units(ndlon, ndgl)
+    ref = LamRef(ndlon, ndgl, M, N, exwn, eywn)
+    r = kresol if kresol is not None else et.esetup_trans(M, N, ndgl, kdlon=ndlon, pexwn=exwn, peywn=eywn, precision=precision)
+    try:
+        assert et.etrans_inq(r, "nspec2") == ref.nspec2 and et.etrans_inq(r, "ngptot") == ref.ngptot
+        npt = ref.ngptot
+        nproma = nproma or npt
+        nb = (npt - 1) // nproma + 1
+        if split:
+            nsc = 6
+        rng = np.random.default_rng(seed)
+        g = rng.uniform(-1.0, 1.0, (2 * nuv + nsc, npt)).astype(dt).astype(np.float64)
+        rv, rd, rs, rmu, rmv = ref.dir_trans(g.reshape(-1, ndgl, ndlon), nuv=nuv, nsc=nsc)
+        pad = lambda a: np.where(a == -777.0, np.nan, a).astype(dt)
+        Z = lambda *shape: to_dev(np.full(shape, -777.0, dtype=dt))
+        gsc = g[2 * nuv:]
+        if not split:
+            dir_in = dict(pgp=to_dev(pad(blocked(g, nproma, dt))))
+            sp_out = dict(pspscalar=Z(ref.nspec2, nsc))
+        else:
+            dir_in = dict(pgp2=to_dev(pad(blocked(gsc[0:1], nproma, dt))),
+                          pgp3a=to_dev(pad(blocked(gsc[1:5], nproma, dt).reshape(nb, 2, 2, nproma))),
+                          pgp3b=to_dev(pad(blocked(gsc[5:6], nproma, dt).reshape(nb, 1, 1, nproma))))
+            if nuv:
+                dir_in["pgpuv"] = to_dev(pad(blocked(g[:2 * nuv], nproma, dt).reshape(nb, 2, nuv, nproma)))
+            sp_out = dict(pspsc2=Z(ref.nspec2, 1), pspsc3a=Z(2, ref.nspec2, 2), pspsc3b=Z(1, ref.nspec2, 1))
+        if nuv:
+            sp_out.update(pspvor=Z(ref.nspec2, nuv), pspdiv=Z(ref.nspec2, nuv), pmeanu=Z(nuv), pmeanv=Z(nuv))
+        et.edir_trans(r, kproma=nproma, mem_space=mem_space, **dir_in, **sp_out)
+        H = lambda a: np.asarray(to_host(a), dtype=np.float64)
+        if split:
+            s3a = H(sp_out["pspsc3a"])
+            got_sc = np.concatenate([H(sp_out["pspsc2"]), s3a[0], s3a[1], H(sp_out["pspsc3b"])[0]], axis=1)
+        else:
+            got_sc = H(sp_out["pspscalar"])
+        errs = {}
+
+        def cmp(label, got, want):
+            for f in range(want.shape[1]):  # NaN in the output counts as infinite
+                e = np.abs(got[:, f] - want[:, f]).max() / max(np.abs(want[:, f]).max(), 1e-300)
+                errs[label] = max(errs.get(label, 0.0), float(e) if np.isfinite(e) else np.inf)
+
+        outs = {"sc": got_sc}
+        cmp("dir sc", got_sc, rs)
+        if nuv:
+            outs["vor"], outs["div"] = H(sp_out["pspvor"]), H(sp_out["pspdiv"])
+            cmp("dir vor", outs["vor"], rv)
+            cmp("dir div", outs["div"], rd)
+            e = np.max(np.abs(np.concatenate([H(sp_out["pmeanu"]) - rmu, H(sp_out["pmeanv"]) - rmv]))) / np.abs(g[:2 * nuv]).max()
+            errs["dir mean"] = float(e) if np.isfinite(e) else np.inf
+        for nm, a in outs.items():  # the entries that do not enter the inverse transform are written as exact zeros
+            assert np.array_equal(ref.clean(a), a), "structural zeros of " + nm
+        yard = None
+        if precision == 4:
+            want = rs[:, :1]
+            y = fp32_lam_direct(ref, gsc[0].reshape(ndgl, ndlon))
+            scale = np.abs(want).max()
+            yard = {"lib": float(np.abs(got_sc[:, :1] - want).max() / scale), "cpu": float(np.abs(y - want).max() / scale)}
+        return errs, yard
+    finally:
+        if kresol is None:
+            et.trans_release(r)

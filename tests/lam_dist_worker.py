@@ -51,6 +51,24 @@ def main():
                   pgp=np.ascontiguousarray(gin[None, :, lat0 * NDLON:lat1 * NDLON]))
     if 0 not in myms:
         assert np.all(mean == -5.0)  # the task that owns m = 0 writes the means
+    # the same leg on full-bandwidth input: the same global white fields on every task, this task's rows in, this task's wavenumbers against
+    # the global model (the emulator tier's bound, tests/test_lam_emu.py); energy above M in every row and outside the ellipse
+    gw = np.random.default_rng(22).uniform(-1.0, 1.0, gin.shape)
+    wv, wd, ws, wmu, wmv = one.dir_trans(gw.reshape(-1, NDGL, NDLON), nuv=NUV, nsc=NSC)
+    v3, d3, s3 = np.zeros((len(idx), NUV)), np.zeros((len(idx), NUV)), np.zeros((len(idx), NSC))
+    mean3 = np.full((2, NUV), -5.0)
+    et.edir_trans(r, pspvor=v3, pspdiv=d3, pspscalar=s3, pmeanu=mean3[0], pmeanv=mean3[1],
+                  pgp=np.ascontiguousarray(gw[None, :, lat0 * NDLON:lat1 * NDLON]))
+    for got, want in ((v3, wv), (d3, wd), (s3, ws)):
+        e = np.abs(got - want[idx]).max(axis=0) / np.abs(want).max(axis=0)
+        assert e.max() < 1e-12, e
+        glob = np.zeros_like(want)
+        glob[idx] = got
+        assert np.array_equal(one.clean(glob), glob)  # the structural zeros
+    if 0 in myms:
+        assert max(np.abs(mean3[0] - wmu).max(), np.abs(mean3[1] - wmv).max()) < 1e-12
+    else:
+        assert np.all(mean3 == -5.0)
     np.savez(os.path.join(outdir, "lam_%d_of_%d.npz" % (rank, world)), grid=gp[0], vor=v2, div=d2, sc=s2, mean=mean,
              **{n: q(n) for n in ("myms", "procm", "latlo", "ndim0g", "nump", "numpp", "nptrms", "nallms", "npossp", "nspec2", "nspec2mx",
                                   "nesm0", "ngptot", "nfrstlat", "nlstlat")})

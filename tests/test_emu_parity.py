@@ -569,3 +569,71 @@ def test_utility_routines_vordiv_to_uv_and_gpnorm(et, precision):
     e_uv, e_sb, e_gp = utility_case(et, Oracle, XP, 15, precision, 37)
     tol = 1e-12 if precision == 8 else 3e-6
     assert e_uv < tol and e_sb < tol and e_gp < tol, (e_uv, e_sb, e_gp)
+
+
+# ---- direct transforms of full-bandwidth (white) grid fields ----------------------------------------------------------------------
+# Every case above hands DIR_TRANS the oracle's own inverse transform of a truncated spectrum: no energy at the zonal wavenumbers
+# m > NMEN(row), which the transform exists to discard.  White fields hold energy at every m of every row.
+BLUE_ROWS = [22, 26, 28, 30, 34, 38, 46, 58, 62]
+ODD_ROWS = [19, 21, 23, 25, 27, 29, 33, 35, 37]
+SERIES_GRIDS = {
+    "O9": (8, SMOOTH + SMOOTH[::-1]),
+    "O22": (21, octahedral(21)),
+    "bluestein_even": (8, BLUE_ROWS + BLUE_ROWS[::-1]),
+    "odd_lengths": (8, ODD_ROWS + ODD_ROWS[::-1]),
+    "regular_48_T23": (23, [48] * 24),
+    "regular_46_T23": (23, [46] * 24),           # NMEN = 22 = NLOEN / 2 - 1 on every row
+    "T31_on_O9": (31, SMOOTH + SMOOTH[::-1]),    # wavenumbers 26 ... 31 lie above every row's NMEN
+    "mixed_radix_long_rows": (15, MR_LONG + MR_LONG[::-1]),
+    "tl149": (148, None),
+}
+
+
+@pytest.mark.parametrize("name", sorted(SERIES_GRIDS))
+def test_oracle_direct_transform_matches_plain_summation_on_white_fields(name, golden_dir):
+    """The oracle's DIR_TRANS of U(-1,1) white fields against tests/common.py::series_direct, the defining double sum in float64 with no
+    FFT and the truncation m <= NMEN(row) written out: the reference of the white cases is itself right where the band-limited cases
+    cannot tell.  Bound 1e-13 of the largest coefficient (observed 3.2e-16 ... 6.3e-16 on the small grids, 1.0e-15 on TL149)."""
+    from tests.common import series_direct
+    nsmax, nloen = SERIES_GRIDS[name]
+    if nloen is None:
+        nloen = np.load(os.path.join(golden_dir, "tl149", "lon_number_by_lat.npy"))
+    nloen = np.asarray(nloen, dtype=np.int32)
+    o = Oracle(nsmax, nloen)
+    g = np.random.default_rng(99).uniform(-1.0, 1.0, (2, o.ngptot))
+    _, _, sr = o.dir_trans(g, nsc=2)
+    want = series_direct(o, nsmax, nloen, g)
+    e = np.abs(sr - want).max() / np.abs(want).max()
+    print(name, "oracle against plain summation: %.2e" % e)
+    assert e < 1e-13, e
+    assert np.all(want[1:2 * (nsmax + 1):2] == 0.0) and np.all(sr[1:2 * (nsmax + 1):2] == 0.0)  # imag(m = 0)
+
+
+WHITE_CASES = dict({k: (v[0], v[1], v[2], v[3], v[5]) for k, v in CASES.items()},
+                   truncation_above_grid=(31, SMOOTH + SMOOTH[::-1], 1, 2, None),
+                   nmen_is_half_row_minus_one=(17, SMOOTH + SMOOTH[::-1], 1, 2, None),  # NSMAX = NDGL - 1: NMEN = (NLOEN - 1) / 2 = 9, 11, ... 17
+                   mixed_radix_short_rows=(15, MR_SHORT[:6] + MR_SHORT[5::-1], 1, 1, None),
+                   nproma_cuts_rows=(8, SMOOTH + SMOOTH[::-1], 1, 2, 23))
+WHITE_CASES["odd_lengths_winds_nproma"] = (8, ODD_ROWS + ODD_ROWS[::-1], 1, 2, 100)  # (with winds and a padded last block: 522 points in blocks of 100)
+
+
+@pytest.mark.parametrize("name", sorted(WHITE_CASES))
+def test_emulated_direct_transform_of_white_fields(et, name):
+    """DIR_TRANS of white grid fields (tests/common.py::white_direct_case; NaN in the padding of the last NPROMA block) against the oracle:
+    1e-12 per field (this tier's bound) and 1e-10 per total wavenumber.  Observed 5.1e-16 ... 7.2e-16 per field, 7.2e-16 ... 7.4e-15 per total wavenumber (the largest on the short mixed-radix rows)."""
+    from tests.common import assert_white, white_direct_case
+    nsmax, nloen, nuv, nsc, nproma = WHITE_CASES[name]
+    res = white_direct_case(et, Oracle, XP, nsmax, nloen, nuv, nsc, nproma)
+    assert_white(res, 8, TOL, 1e-10, name)
+
+
+@pytest.mark.parametrize("name", ["octahedral_winds", "truncation_above_grid", "nproma_cuts_rows"])
+def test_emulated_fp32_direct_transform_of_white_fields(et, name):
+    """The same in the fp32 library: 2e-5 per field (this tier's fp32 bound) and, on the first scalar field, at most 3 x the error of the plain
+    float32 CPU chain fp32_columns_direct, both against the fp64 oracle.  Observed: all fields 1.9e-7 ... 2.4e-7 per field, 3.4e-7 ... 4.7e-7 per total wavenumber; on the first scalar the library 0.9e-7 ... 1.5e-7
+    per field and 3.4e-7 per total wavenumber, the yardstick 1.3e-7 and 1.9e-7."""
+    from tests.common import assert_white, white_direct_case
+    nsmax, nloen, nuv, nsc, nproma = WHITE_CASES[name]
+    res = white_direct_case(et, Oracle, XP, nsmax, nloen, nuv, nsc, nproma, precision=4)
+    assert_white(res, 4, 2e-5, None, name)
+    assert res["field"] > 1e-9  # really computed in float

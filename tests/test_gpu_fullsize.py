@@ -172,3 +172,31 @@ def test_tco1279_sharded_over_8_tasks_on_one_gpu(tmp_path):
         err = np.abs(a[k] - b[k]).max() / np.abs(a[k]).max()
         assert err < 1e-13, (k, err)
     assert np.array_equal(a["crc"], b["crc"]), (a["crc"], b["crc"])
+
+
+# ---- direct transforms of full-bandwidth (white) grid fields at the sizes above ---------------------------------------------------------
+# The base fields of the direct leg are U(-1,1) white noise (full_size_call_mode2(white=True)): on an octahedral grid most rows have
+# NMEN < NSMAX, so most (row, zonal wavenumber) pairs hold energy that DIR_TRANS must discard, and the flat spectrum makes the
+# per-total-wavenumber measure `dir_n` sharp at every n.  The band-limited tests above cannot see that energy.
+def test_tco399_white_direct_input_matches_oracle(et):
+    """TCo399, KF = 823, fp64: every field against c_f x the oracle's direct transform of its white base field; 1e-11 per field, 1e-10 per
+    total wavenumber.  Observed on an MI355X: direct 2.5e-14 per field (rms 4.3e-16), 7.2e-15 per total wavenumber; inverse 1.9e-14."""
+    res = full_size_call_mode2(et, Oracle, 399, 137, 4, precision=8, tol=1e-11, tol_norm=1e-10, tol_group=1e-10, white=True)
+    print("TCo399 KF=823 white:", res)
+
+
+def test_tco399_fp32_white_direct_input_matches_oracle(et):
+    """TCo399, KF = 823, fp32 library: the direct leg at the project's 3e-5 per field, and the float32 CPU yardstick of
+    test_tco399_fp32_against_float32_cpu_yardstick (HIP error <= 3 x that of fp32_columns_direct on the same white field, on the sampled
+    and the three worst zonal wavenumbers); the inverse leg keeps that test's bounds.  Observed on an MI355X: direct 1.04e-5 per field (rms 1.6e-7), 3.1e-6 per
+    total wavenumber; on the yardstick's wavenumbers the library 8.3e-7, the yardstick 1.6e-7, ratio 1.75 after the floor of 4 epsilons."""
+    ys = dict(lats=[1, 3, 50, 200, 400], ms=[0, 1, 5, 200, 399], factor=3.0)
+    res = full_size_call_mode2(et, Oracle, 399, 137, 4, precision=4, tol=1e-4, tol_dir=3e-5, tol_norm=1e-5, tol_rms=5e-6, yardstick=ys, white=True)
+    print("TCo399 fp32 KF=823 white:", res)
+
+
+def test_tco1279_white_direct_input_matches_oracle(et):
+    """TCo1279, KF = 1645, fp64 -- bench.py's arrays -- with white direct input: 1e-11 per field, 1e-10 per total wavenumber.
+    Observed on an MI355X: direct 7.9e-14 per field (rms 7.0e-16), 1.4e-14 per total wavenumber; inverse 5.4e-14."""
+    res = full_size_call_mode2(et, Oracle, 1279, 137, 10, precision=8, tol=1e-11, tol_norm=1e-10, tol_group=1e-10, white=True)
+    print("TCo1279 KF=1645 white:", res)

@@ -312,3 +312,34 @@ def test_tasks_assemble_to_the_one_task_result(nproc, tmp_path):
     for k in spec:
         assert spec[k].tobytes() == one[k].tobytes(), k
     assert mean.tobytes() == one["mean"].tobytes()
+
+
+# ---- 8. direct transforms of full-bandwidth (white) grid fields -----------------------------------------------------------------------
+# lam_case hands EDIR_TRANS the model's own inverse transform: no energy above KMSMAX in a row or outside the ellipse, which the transform
+# exists to discard.  White fields hold energy in every wavenumber pair.
+WHITE = ["golden_size", "split_arrays_nproma", "odd_x_prime_y", "prime_x_factor7_y", "factor11_both", "factor7_x_odd_y", "m_zero", "n_zero"]
+
+
+@pytest.mark.parametrize("name", WHITE)
+def test_white_direct_fp64(et, name):
+    """tests/lam_common.py::lam_white_case: vorticity, divergence, scalars, mean wind and the structural zeros against the model, NaN in the
+    padding of the last NPROMA block.  Observed 1.7e-16 ... 1.0e-15 on vorticity, divergence and scalars, at most 1.4e-17 on the mean wind."""
+    from tests.lam_common import lam_white_case
+    ndlon, ndgl, M, N, kw = CASES[name]
+    errs, _ = lam_white_case(et, ndlon, ndgl, M, N, **kw)
+    print(name, {k: "%.1e" % v for k, v in errs.items()})
+    assert max(errs.values()) < TOL, errs
+
+
+@pytest.mark.parametrize("name", ["split_arrays_nproma", "odd_x_prime_y"])
+def test_white_direct_fp32(et, name):
+    """The same in the fp32 library: the project's 3e-5 and, on the first scalar field, at most 3 x the error of the float32 yardstick
+    (scipy's single-precision FFTs on float32 data, tests/lam_common.py::fp32_lam_direct), the denominator floored at 4 float32 epsilons:
+    the rule of tests/test_gpu_fullsize.py.  Observed: all fields 1.5e-7 ... 2.4e-7; on the first scalar the library 1.5e-7 and 1.7e-7, the yardstick 1.2e-7 and 1.5e-7."""
+    from tests.lam_common import lam_white_case
+    ndlon, ndgl, M, N, kw = CASES[name]
+    errs, yard = lam_white_case(et, ndlon, ndgl, M, N, precision=4, **kw)
+    print(name, {k: "%.1e" % v for k, v in errs.items()}, yard)
+    assert max(errs.values()) < TOL32, errs
+    assert max(errs.values()) > 1e-9  # really computed in float
+    assert yard["lib"] <= 3.0 * max(yard["cpu"], 4 * np.finfo(np.float32).eps), yard
