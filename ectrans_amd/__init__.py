@@ -11,7 +11,7 @@ Arrays are passed with the *Fortran* index order reversed (C-contiguous):
 ``(ngpblks, nfld, nproma)``, ``PSPSC3A(nlev, nspec2, nvar)`` is ``(nvar, nspec2, nlev)``,
 ``PGPUV(nproma, nlev, nvar, ngpblks)`` is ``(ngpblks, nvar, nlev, nproma)``.
 numpy arrays are staged through PCIe (EMI_MEM_HOST); torch CUDA tensors are used in place
-(EMI_MEM_DEVICE).  There is no CPU implementation in this package: without the HIP library
+(EMI_MEM_DEVICE); the ``mem_space`` keyword of the calls that take arrays overrides this.  There is no CPU implementation in this package: without the HIP library
 and a GPU every call fails loudly.
 """
 import ctypes as C
@@ -207,6 +207,11 @@ def _ptr(a, space):
     elif space[0] != EMI_MEM_HOST:
         raise TransError("all arrays of one call must live in the same memory space")
     return a.ctypes.data, a
+
+
+def _space(mem_space, space):
+    """The memory space of a call: `mem_space` where the caller gives one, else what the arrays said (host where there are none)."""
+    return int(mem_space) if mem_space is not None else space[0] if space[0] is not None else EMI_MEM_HOST
 
 
 _DIST = {"nproc": 1, "nprtrv": 1, "group": None, "device": None}
@@ -428,10 +433,12 @@ def _fill_vsets(a, keep, kvsetuv, kvsetsc, kvsetsc2, kvsetsc3a, kvsetsc3b, pgp3a
 def inv_trans(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, pspsc3b=None, pspsc2=None,
               ldscders=False, ldvorgp=False, lddivgp=False, lduvder=False, kproma=None, pgp=None, pgpuv=None,
               pgp3a=None, pgp3b=None, pgp2=None, stream=None, kvsetuv=None, kvsetsc=None, kvsetsc2=None, kvsetsc3a=None,
-              kvsetsc3b=None, ldlatlon=False):
+              kvsetsc3b=None, ldlatlon=False, mem_space=None):
     """INV_TRANS (inv_trans.h:12-163): spectral -> grid point, results written into pgp*/...
 
-    ldlatlon: the output is the lat-lon grid of a handle set up with ``ldll`` (required there, refused elsewhere)."""
+    ldlatlon: the output is the lat-lon grid of a handle set up with ``ldll`` (required there, refused elsewhere).
+    mem_space: overrides the memory space derived from the arrays (EMI_MEM_AUTO; on the CPU emulator of the tests EMI_MEM_DEVICE uses
+    numpy arrays in place, the path device tensors take on a GPU)."""
     a, space, keep = _Inv(), [None, real_dtype(kresol)], []
     nspec2, ngptot = trans_inq(kresol, "nspec2"), trans_inq(kresol, "ngptot")
     nproma = int(kproma) if kproma else ngptot
@@ -442,7 +449,7 @@ def inv_trans(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, ps
     a.ldscders, a.ldvorgp, a.lddivgp, a.lduvder = int(ldscders), int(ldvorgp), int(lddivgp), int(lduvder)
     a.kproma = nproma
     a.ldlatlon = int(bool(ldlatlon))
-    a.mem_space = space[0] if space[0] is not None else EMI_MEM_HOST
+    a.mem_space = _space(mem_space, space)
     a.stream = stream
     _fill_vsets(a, keep, kvsetuv, kvsetsc, kvsetsc2, kvsetsc3a, kvsetsc3b, pgp3a, pgp3b, 3 if ldscders else 1)
     _chk(lib().emi_inv_trans(kresol, C.byref(a)))
@@ -450,8 +457,10 @@ def inv_trans(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, ps
 
 def dir_trans(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, pspsc3b=None, pspsc2=None,
               kproma=None, pgp=None, pgpuv=None, pgp3a=None, pgp3b=None, pgp2=None, stream=None, kvsetuv=None, kvsetsc=None,
-              kvsetsc2=None, kvsetsc3a=None, kvsetsc3b=None):
-    """DIR_TRANS (dir_trans.h:12-140): grid point -> spectral, results written into psp*."""
+              kvsetsc2=None, kvsetsc3a=None, kvsetsc3b=None, mem_space=None):
+    """DIR_TRANS (dir_trans.h:12-140): grid point -> spectral, results written into psp*.
+    mem_space: overrides the memory space derived from the arrays (EMI_MEM_AUTO; on the CPU emulator of the tests EMI_MEM_DEVICE uses
+    numpy arrays in place, the path device tensors take on a GPU)."""
     a, space, keep = _Dir(), [None, real_dtype(kresol)], []
     nspec2, ngptot = trans_inq(kresol, "nspec2"), trans_inq(kresol, "ngptot")
     nproma = int(kproma) if kproma else ngptot
@@ -460,7 +469,7 @@ def dir_trans(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, ps
     _fill_grid(a, space, keep, pgp, pgpuv, pgp3a, pgp3b, pgp2, nproma, ngpblks,
                (pspvor, pspdiv, pspscalar, pspsc3a, pspsc3b, pspsc2))
     a.kproma = nproma
-    a.mem_space = space[0] if space[0] is not None else EMI_MEM_HOST
+    a.mem_space = _space(mem_space, space)
     a.stream = stream
     _fill_vsets(a, keep, kvsetuv, kvsetsc, kvsetsc2, kvsetsc3a, kvsetsc3b, pgp3a, pgp3b)
     _chk(lib().emi_dir_trans(kresol, C.byref(a)))
@@ -469,11 +478,13 @@ def dir_trans(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, ps
 def inv_transad(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, pspsc3b=None, pspsc2=None,
                 ldscders=False, ldvorgp=False, lddivgp=False, lduvder=False,
                 kproma=None, pgp=None, pgpuv=None, pgp3a=None, pgp3b=None, pgp2=None, stream=None, kvsetuv=None, kvsetsc=None,
-                kvsetsc2=None, kvsetsc3a=None, kvsetsc3b=None):
+                kvsetsc2=None, kvsetsc3a=None, kvsetsc3b=None, mem_space=None):
     """INV_TRANSAD (inv_transad.h:12): adjoint of INV_TRANS -- reads pgp*, writes psp* (overwritten).
     Inner products: plain sum in grid-point space, SPECNORM weights (1 for m = 0, 2 for m > 0) in
     spectral space, as tests/trans/test_invtrans_adjoint.F90:243-315.  With ldscders / ldvorgp / lddivgp / lduvder the
-    grid arrays carry the derivative / vorticity / divergence inputs in INV_TRANS's layout (inv_trans.h:66-76)."""
+    grid arrays carry the derivative / vorticity / divergence inputs in INV_TRANS's layout (inv_trans.h:66-76).
+    mem_space: overrides the memory space derived from the arrays (EMI_MEM_AUTO; on the CPU emulator of the tests EMI_MEM_DEVICE uses
+    numpy arrays in place, the path device tensors take on a GPU)."""
     a, space, keep = _Inv(), [None, real_dtype(kresol)], []
     nspec2, ngptot = trans_inq(kresol, "nspec2"), trans_inq(kresol, "ngptot")
     nproma = int(kproma) if kproma else ngptot
@@ -482,7 +493,7 @@ def inv_transad(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, 
                (pspvor, pspdiv, pspscalar, pspsc3a, pspsc3b, pspsc2))
     a.ldscders, a.ldvorgp, a.lddivgp, a.lduvder = int(ldscders), int(ldvorgp), int(lddivgp), int(lduvder)
     a.kproma = nproma
-    a.mem_space = space[0] if space[0] is not None else EMI_MEM_HOST
+    a.mem_space = _space(mem_space, space)
     a.stream = stream
     _fill_vsets(a, keep, kvsetuv, kvsetsc, kvsetsc2, kvsetsc3a, kvsetsc3b, pgp3a, pgp3b, 3 if ldscders else 1)
     _chk(lib().emi_inv_transad(kresol, C.byref(a)))
@@ -490,8 +501,10 @@ def inv_transad(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, 
 
 def dir_transad(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, pspsc3b=None, pspsc2=None,
                 kproma=None, pgp=None, pgpuv=None, pgp3a=None, pgp3b=None, pgp2=None, stream=None, kvsetuv=None, kvsetsc=None,
-                kvsetsc2=None, kvsetsc3a=None, kvsetsc3b=None):
-    """DIR_TRANSAD (dir_transad.h:12): adjoint of DIR_TRANS -- reads psp*, writes pgp*."""
+                kvsetsc2=None, kvsetsc3a=None, kvsetsc3b=None, mem_space=None):
+    """DIR_TRANSAD (dir_transad.h:12): adjoint of DIR_TRANS -- reads psp*, writes pgp*.
+    mem_space: overrides the memory space derived from the arrays (EMI_MEM_AUTO; on the CPU emulator of the tests EMI_MEM_DEVICE uses
+    numpy arrays in place, the path device tensors take on a GPU)."""
     a, space, keep = _Dir(), [None, real_dtype(kresol)], []
     nspec2, ngptot = trans_inq(kresol, "nspec2"), trans_inq(kresol, "ngptot")
     nproma = int(kproma) if kproma else ngptot
@@ -499,7 +512,7 @@ def dir_transad(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, 
     _fill_grid(a, space, keep, pgp, pgpuv, pgp3a, pgp3b, pgp2, nproma, (ngptot - 1) // nproma + 1,
                (pspvor, pspdiv, pspscalar, pspsc3a, pspsc3b, pspsc2))
     a.kproma = nproma
-    a.mem_space = space[0] if space[0] is not None else EMI_MEM_HOST
+    a.mem_space = _space(mem_space, space)
     a.stream = stream
     _fill_vsets(a, keep, kvsetuv, kvsetsc, kvsetsc2, kvsetsc3a, kvsetsc3b, pgp3a, pgp3b)
     _chk(lib().emi_dir_transad(kresol, C.byref(a)))
@@ -574,7 +587,7 @@ def einv_trans(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, p
     a.ldscders, a.ldvorgp, a.lddivgp, a.lduvder = int(ldscders), int(ldvorgp), int(lddivgp), int(lduvder)
     a.kproma = nproma
     mu, mv = _mean_ptr(pmeanu, a.nf_uv, space, keep, "PMEANU"), _mean_ptr(pmeanv, a.nf_uv, space, keep, "PMEANV")
-    a.mem_space = int(mem_space) if mem_space is not None else space[0] if space[0] is not None else EMI_MEM_HOST
+    a.mem_space = _space(mem_space, space)
     a.stream = stream
     _chk(lib().emi_einv_trans(kresol, C.byref(a), mu, mv))
 
@@ -595,7 +608,7 @@ def edir_trans(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, p
                (pspvor, pspdiv, pspscalar, pspsc3a, pspsc3b, pspsc2))
     a.kproma = nproma
     mu, mv = _mean_ptr(pmeanu, a.nf_uv, space, keep, "PMEANU"), _mean_ptr(pmeanv, a.nf_uv, space, keep, "PMEANV")
-    a.mem_space = int(mem_space) if mem_space is not None else space[0] if space[0] is not None else EMI_MEM_HOST
+    a.mem_space = _space(mem_space, space)
     a.stream = stream
     _chk(lib().emi_edir_trans(kresol, C.byref(a), mu, mv))
 
@@ -634,15 +647,18 @@ def etrans_inq(kresol, name):
     raise TransError("ETRANS_INQ: unknown quantity %r" % name)
 
 
-def specnorm(kresol, pspec, kvset=None):
+def specnorm(kresol, pspec, kvset=None, mem_space=None):
     """SPECNORM (specnorm.h:12): per-field spectral L2 norm, returned as a numpy array (on every
     task; the reference returns it on the master only).  kvset (NPRTRV > 1, specnorm.F90:82-101): V-set of every GLOBAL
-    field; pspec holds this task's fields of its own V-set and the norms of all len(kvset) fields come back."""
+    field; pspec holds this task's fields of its own V-set and the norms of all len(kvset) fields come back.
+    mem_space: overrides the memory space derived from the arrays (EMI_MEM_AUTO; on the CPU emulator of the tests EMI_MEM_DEVICE uses
+    numpy arrays in place, the path device tensors take on a GPU)."""
     space = [None, real_dtype(kresol)]
     if pspec.shape[1] == 0:
         p, keep, space[0] = None, None, EMI_MEM_HOST
     else:
         p, keep = _ptr(pspec, space)
+        space[0] = _space(mem_space, space)
     pd = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
     if kvset is not None and _DIST.get("nprtrv", 1) > 1:
         kv = np.ascontiguousarray(kvset, dtype=np.int32)
@@ -659,12 +675,15 @@ def specnorm(kresol, pspec, kvset=None):
     return np.sqrt(_dist.all_reduce_sum(out, _DIST["group"], _DIST["device"]))  # every task gets the norms
 
 
-def gpnorm_trans(kresol, pgp, kfields=None, kproma=None, ldave_only=False, pmin=None, pmax=None):
+def gpnorm_trans(kresol, pgp, kfields=None, kproma=None, ldave_only=False, pmin=None, pmax=None, mem_space=None):
     """GPNORM_TRANS (gpnorm_trans.h:12): (PAVE, PMIN, PMAX) of the first `kfields` fields of pgp[ngpblks, nfld, nproma] -- the
     area-weighted average over the sphere (Gaussian weights), minimum and maximum -- as numpy arrays, on every task (the
-    reference: task 1).  ldave_only: pmin / pmax are the caller's local extrema and are only reduced over the tasks."""
+    reference: task 1).  ldave_only: pmin / pmax are the caller's local extrema and are only reduced over the tasks.
+    mem_space: overrides the memory space derived from the arrays (EMI_MEM_AUTO; on the CPU emulator of the tests EMI_MEM_DEVICE uses
+    numpy arrays in place, the path device tensors take on a GPU)."""
     space = [None, real_dtype(kresol)]
     p, keep = _ptr(pgp, space)
+    space[0] = _space(mem_space, space)
     if pgp.ndim != 3:
         raise TransError("PGP must have 3 dimensions (ngpblks, fields, nproma), got shape %s" % (tuple(pgp.shape),))
     nf = int(pgp.shape[1]) if kfields is None else int(kfields)
@@ -677,9 +696,11 @@ def gpnorm_trans(kresol, pgp, kfields=None, kproma=None, ldave_only=False, pmin=
     return ave, mn, mx
 
 
-def vordiv_to_uv(pspvor, pspdiv, ksmax, pspu=None, pspv=None):
+def vordiv_to_uv(pspvor, pspdiv, ksmax, pspu=None, pspv=None, mem_space=None):
     """VORDIV_TO_UV (vordiv_to_uv.h:12): spectral vorticity / divergence [nspec2, nfld] -> spectral (U, V) = (u, v) cos(theta), total
-    wavenumbers n <= ksmax, for the zonal wavenumbers of this task.  Needs setup_trans0 only; returns (pspu, pspv)."""
+    wavenumbers n <= ksmax, for the zonal wavenumbers of this task.  Needs setup_trans0 only; returns (pspu, pspv).
+    mem_space: overrides the memory space derived from the arrays (EMI_MEM_AUTO; on the CPU emulator of the tests EMI_MEM_DEVICE uses
+    numpy arrays in place, the path device tensors take on a GPU)."""
     is64 = str(pspvor.dtype).endswith("float64")
     space = [None, "float64" if is64 else "float32"]
     pv_, k1 = _ptr(pspvor, space)
@@ -692,7 +713,7 @@ def vordiv_to_uv(pspvor, pspdiv, ksmax, pspu=None, pspv=None):
     pw_, k4 = _ptr(pspv, space)
     if not (tuple(pspvor.shape) == tuple(pspdiv.shape) == tuple(pspu.shape) == tuple(pspv.shape)) or pspvor.ndim != 2:
         raise TransError("VORDIV_TO_UV: PSPVOR, PSPDIV, PSPU, PSPV must be [nspec2, nfld] arrays of one shape")
-    _chk(lib().emi_vordiv_to_uv(int(ksmax), 8 if is64 else 4, space[0], pv_, pd_, pu_, pw_, int(pspvor.shape[1]), int(pspvor.shape[0])))
+    _chk(lib().emi_vordiv_to_uv(int(ksmax), 8 if is64 else 4, _space(mem_space, space), pv_, pd_, pu_, pw_, int(pspvor.shape[1]), int(pspvor.shape[0])))
     return pspu, pspv
 
 

@@ -886,3 +886,300 @@ def utility_case(et, oracle_cls, dev, nsmax=21, precision=8, nproma=37):
     assert list(mn2) == [-1.0, -2.0] and list(mx2) == [3.0, 4.0] and np.abs(a2 - a1[:2]).max() == 0.0
     et.trans_release(r)
     return e_uv, e_sb, e_gp
+
+
+# ---- caller-placed arrays: odd offsets, guard bands, inputs intact -----------------------------------------------------------------
+def _bits(a):
+    """the bit patterns of a float array (NaN payloads count)"""
+    a = np.ascontiguousarray(a)
+    return a.view(np.int64 if a.dtype == np.float64 else np.int32)
+
+
+def _finite_err(got, want, axis=None):
+    """rel_err, a NaN or an infinity in `got` counting as an infinite error"""
+    got = np.asarray(got, dtype=np.float64)
+    return float(rel_err(got, want, axis=axis)) if np.all(np.isfinite(got)) else np.inf
+
+
+def guard_for(longest_row):
+    """a guard band for GuardedSpace: a multiple of 64 elements, at least the longest row + 64, so that `lead` alone decides the alignment
+    of the array and an access one row too far still lands in the guard"""
+    return 64 * ((int(longest_row) + 64 + 63) // 64)
+
+
+class GuardedSpace:
+    """Arrays placed as a caller places them: each inside a larger flat buffer of the memory under test, `guard` sentinel elements below
+    and above it and `lead` more below (lead = 1: the array starts on an odd element).  to_flat(numpy 1-D) -> the flat buffer (a torch
+    device tensor on the GPU, the numpy array itself on the emulator); back(buffer or view) -> numpy of the same dtype.  All
+    comparisons are on bit patterns."""
+    SENTINEL = -7.25e3
+
+    def __init__(self, lead, guard, to_flat, back):
+        assert guard % 64 == 0 and guard > 0 and lead >= 0
+        self.lead, self.guard, self.to_flat, self.back = lead, guard, to_flat, back
+        self.recs = []  # [buffer, view, bit copy of the initial content, role]
+
+    def put(self, array, role):
+        """the contiguous view with `array`'s shape and content at element offset guard + lead of a new sentinel-filled buffer;
+        role "in": check() compares it with its initial bits, "out": only its guard bands are watched"""
+        assert role in ("in", "out")
+        a = np.ascontiguousarray(array)
+        o = self.guard + self.lead
+        flat = np.full(o + a.size + self.guard, self.SENTINEL, dtype=a.dtype)
+        flat[o:o + a.size] = a.reshape(-1)
+        buf = self.to_flat(flat)
+        view = buf[o:o + a.size].reshape(a.shape)
+        self.recs.append([buf, view, _bits(a).copy(), role])
+        return view
+
+    def _rec(self, view):
+        return next(rec for rec in self.recs if rec[1] is view)
+
+    def set_role(self, view, role):
+        self._rec(view)[3] = role
+
+    def check(self):
+        """after a library call: the violations (strings) -- a guard band that differs from the sentinel, with the first offsets
+        relative to the array's first element, and an "in" array that differs from its initial bits"""
+        bad = []
+        for k, (buf, view, bits0, role) in enumerate(self.recs):
+            h = _bits(self.back(buf))
+            o, n = self.guard + self.lead, bits0.size
+            s = _bits(np.full(1, self.SENTINEL, dtype=bits0.dtype.name.replace("int", "float")))[0]
+            what = "array %d (%s, shape %s, lead %d)" % (k, role, tuple(bits0.shape), self.lead)
+            for name, lo, hi in (("below", 0, o), ("above", o + n, h.size)):
+                w = np.flatnonzero(h[lo:hi] != s)
+                if w.size:
+                    bad.append("%s: %d guard elements %s it written, first at offsets %s" % (what, w.size, name, list(w[:8] + lo - o)))
+            if role == "in":
+                w = np.flatnonzero(h[o:o + n] != bits0.reshape(-1))
+                if w.size:
+                    bad.append("%s: %d elements of an input changed, first at flat indices %s" % (what, w.size, list(w[:8])))
+        return bad
+
+    def untouched(self, view, mask, what):
+        """the elements of `view` under `mask` (padding, surplus fields) still hold their initial bits: the violations"""
+        w = np.flatnonzero((_bits(self.back(view)) != self._rec(view)[2])[mask])
+        return ["%s: %d elements that the call must leave alone changed, first (among them) %s" % (what, w.size, list(w[:8]))] if w.size else []
+
+
+_LDFLAGS = (("scders", "ldscders"), ("vorgp", "ldvorgp"), ("divgp", "lddivgp"), ("uvder", "lduvder"))
+_PLACED_REF = {}
+
+
+def placed_reference(Oracle, nsmax, nloen, nuv, nsc, flags, precision, seed=1):
+    """The inputs of placed_arrays_case (rounded to the library precision) and the oracle's answers, computed once per case and
+    shared by the runs at every `lead`; read-only."""
+    key = (nsmax, tuple(int(n) for n in nloen), nuv, nsc, tuple(sorted(flags.items())), precision, seed)
+    if key not in _PLACED_REF:
+        dt = np.float32 if precision == 4 else np.float64
+        rnd = lambda a: a.astype(dt).astype(np.float64)
+        o = Oracle(nsmax, nloen)
+        rng = np.random.default_rng(seed)
+        vor, div = (rnd(random_spectrum(rng, o.nasm0, nsmax, o.nspec2, nuv, True)) for _ in range(2))
+        sc = rnd(random_spectrum(rng, o.nasm0, nsmax, o.nspec2, nsc, False))
+        gref = o.inv_trans(spvor=vor, spdiv=div, spsc=sc, **flags)
+        off = (nuv if flags.get("vorgp") else 0) + (nuv if (flags.get("divgp") or flags.get("vorgp")) else 0)
+        gdir = rnd(gref[off:off + 2 * nuv + nsc])
+        vr, dr, sr = o.dir_trans(gdir, nuv=nuv, nsc=nsc)
+        ref = dict(ns2=o.nspec2, ng=o.ngptot, vor=vor, div=div, sc=sc, gref=gref, gdir=gdir, vr=vr, dr=dr, sr=sr)
+        for v in ref.values():
+            if isinstance(v, np.ndarray):
+                v.setflags(write=False)
+        _PLACED_REF[key] = ref
+    return _PLACED_REF[key]
+
+
+def placed_arrays_case(et, Oracle, mem, nsmax, nloen, nuv, nsc, flags=None, nproma=None, precision=8, lead=0, mem_space=None,
+                       adjoint=False):
+    """INV_TRANS and DIR_TRANS (adjoint: INV_TRANSAD and DIR_TRANSAD) on arrays placed as a caller places them (GuardedSpace: element
+    offset `lead` inside sentinel-filled buffers), used in place.  mem = (to_flat, back) of the memory under test; mem_space: for the
+    emulator (EMI_MEM_DEVICE: numpy arrays in place).  Every output is pre-filled with NaN; the grid arrays carry one surplus field and
+    the padding of the last NPROMA block (kproma = ngptot + 5 where no NPROMA is given: padding without cut rows), both NaN in the inputs.
+    Checked here: the guard bands, the inputs bit for bit, the padding and the surplus field of the outputs bit for bit (-> violations).
+    Forward: errs = {"inv", "dir"} against the oracle (inputs rounded to the library precision first), NaN counting as infinite.
+    Adjoint: errs = {"inv_transad", "dir_transad"} against the same calls on plainly allocated arrays with zero padding (the adjoints
+    themselves are pinned by adjoint_case and the transposed-oracle cases).  Returns (errs, violations, outs): outs = the defined
+    elements of every output as float64, for the comparison between two values of `lead`."""
+    flags = dict(flags or {})
+    to_flat, back = mem
+    dt = np.float32 if precision == 4 else np.float64
+    nloen = np.asarray(nloen, dtype=np.int32)
+    H = lambda v: np.asarray(back(v), dtype=np.float64)
+    kw = {k2: bool(flags.get(k1, False)) for k1, k2 in _LDFLAGS}
+    r = et.setup_trans(nsmax, len(nloen), nloen, precision=precision)
+    try:
+        ns2, ng = et.trans_inq(r, "nspec2"), et.trans_inq(r, "ngptot")
+        npr = nproma or ng + 5
+        nb = (ng - 1) // npr + 1
+        assert nb * npr > ng  # there is padding
+        space = GuardedSpace(lead, guard_for(nloen.max()), to_flat, back)
+        defined = (np.arange(nb * npr) < ng).reshape(nb, 1, npr)
+        lv = flags.get("vorgp", False)
+        ngp = 2 * nuv + nsc + (2 * nsc if flags.get("scders") else 0) + (nuv if lv else 0) + \
+            (nuv if (flags.get("divgp") or lv) else 0) + (2 * nuv if flags.get("uvder") else 0)  # the fields INV_TRANS produces
+        ndir = 2 * nuv + nsc
+
+        def grid(g, fill):
+            """(nf, ngptot) -> the blocked array with one surplus field, padding and surplus field = fill"""
+            out = np.full((nb, g.shape[0] + 1, npr), fill, dtype=dt)
+            out[:, :-1, :] = block(g, npr, fill=fill)
+            return out
+
+        def mask(nf):
+            """the defined elements of a blocked array with nf fields + one surplus field"""
+            m = np.zeros((nb, nf + 1, npr), dtype=bool)
+            m[:, :nf, :] = defined
+            return m
+
+        full = lambda shape, v: np.full(shape, v, dtype=dt)
+        errs, viol, outs = {}, [], {}
+        if not adjoint:
+            ref = placed_reference(Oracle, nsmax, nloen, nuv, nsc, flags, precision)
+            assert (ref["ns2"], ref["ng"], ref["gref"].shape[0]) == (ns2, ng, ngp)
+            # ---- INV_TRANS
+            pv, pd, ps = (space.put(ref[k].astype(dt), "in") for k in ("vor", "div", "sc"))
+            gp = space.put(full((nb, ngp + 1, npr), np.nan), "out")
+            et.inv_trans(r, pspvor=pv, pspdiv=pd, pspscalar=ps, pgp=gp, kproma=npr, mem_space=mem_space, **kw)
+            viol += space.check()
+            viol += space.untouched(gp, ~mask(ngp), "INV_TRANS: padding and surplus field of PGP")
+            outs["inv"] = unblock(H(gp)[:, :ngp], ng)
+            errs["inv"] = _finite_err(outs["inv"], ref["gref"], axis=1)
+            # ---- DIR_TRANS
+            gin = space.put(grid(ref["gdir"], np.nan), "in")
+            v2, d2, s2 = (space.put(full((ns2, k), np.nan), "out") for k in (nuv, nuv, nsc))
+            et.dir_trans(r, pspvor=v2, pspdiv=d2, pspscalar=s2, pgp=gin, kproma=npr, mem_space=mem_space)
+            viol += space.check()
+            outs.update(vor=H(v2), div=H(d2), sc=H(s2))
+            errs["dir"] = max(_finite_err(outs[k], ref[q]) for k, q in (("vor", "vr"), ("div", "dr"), ("sc", "sr")))
+        else:
+            rng = np.random.default_rng(77)
+            yg = rng.uniform(-1, 1, (ngp, ng)).astype(dt)  # grid input of INV_TRANSAD
+            ys = [rng.uniform(-1, 1, (ns2, k)).astype(dt) for k in (nuv, nuv, nsc)]  # spectral inputs of DIR_TRANSAD
+
+            def calls(put, fill):
+                """both adjoints; -> (outputs, the written grid array)"""
+                a = [put(full((ns2, k), fill), "out") for k in (nuv, nuv, nsc)]
+                et.inv_transad(r, pspvor=a[0], pspdiv=a[1], pspscalar=a[2], pgp=put(grid(yg, fill), "in"), kproma=npr,
+                               mem_space=mem_space, **kw)
+                bad = space.check()
+                b = put(full((nb, ndir + 1, npr), fill), "out")
+                et.dir_transad(r, pspvor=put(ys[0], "in"), pspdiv=put(ys[1], "in"), pspscalar=put(ys[2], "in"), pgp=b, kproma=npr,
+                               mem_space=mem_space)
+                bad += space.check()
+                return dict(ad_vor=H(a[0]), ad_div=H(a[1]), ad_sc=H(a[2]), ad_grid=unblock(H(b)[:, :ndir], ng)), b, bad
+
+            plain = lambda x, role: to_flat(np.ascontiguousarray(x).reshape(-1)).reshape(x.shape)
+            want, _, _ = calls(plain, 0.0)  # the control: plainly allocated arrays, zero padding (space holds no array yet)
+            assert all(np.all(np.isfinite(v)) for v in want.values())
+            outs, b, viol = calls(space.put, np.nan)
+            viol += space.untouched(b, ~mask(ndir), "DIR_TRANSAD: padding and surplus field of PGP")
+            errs["inv_transad"] = max(_finite_err(outs[k], want[k]) for k in ("ad_vor", "ad_div", "ad_sc"))
+            errs["dir_transad"] = _finite_err(outs["ad_grid"], want["ad_grid"], axis=1)
+        return errs, viol, outs
+    finally:
+        et.trans_release(r)
+
+
+def assert_placed(run, precision, tol, what="", control=None):
+    """run = the result of placed_arrays_case: no violations, and every error below `tol`, the oracle bound of the tier (the adjoints in
+    fp64: 1e-13 against their plainly allocated control; in fp32 `tol` -- the control and the run are the same float32 computation, each
+    within `tol` of the exact adjoint, so that this asks more than the two bounds together).  control = the result at lead 0 of the same
+    case: in fp64 the outputs of the two leads agree to 1e-13, the bound of the "two kernels, one transform" cases of
+    tests/test_gpu_parity.py (the flat and the element path are different instruction streams, so no bit identity is asked; fp32 gets no
+    agreement bound, each run is held to `tol`)."""
+    errs, viol, outs = run
+    print("placed arrays", what, "precision", precision, {k: "%.2e" % v for k, v in errs.items()}, "violations:", len(viol))
+    agree = {}
+    if control is not None and precision == 8:
+        agree = {k: _finite_err(outs[k], control[2][k], axis=1 if k in ("inv", "ad_grid") else None) for k in outs}
+        print("placed arrays", what, "against lead 0:", {k: "%.2e" % v for k, v in agree.items()})
+    assert not viol, (what, viol)
+    for k, e in errs.items():
+        bound = 1e-13 if (k.endswith("transad") and precision == 8) else tol
+        assert e < bound, (what, k, e, bound)
+    for k, e in agree.items():
+        assert e < 1e-13, (what, k, e)
+
+
+def placed_call_mode2_case(et, Oracle, mem, lead, nsmax=31, nproma=53, mem_space=None):
+    """The call-mode-2 arrays (PGPUV / PGP3A / PGP2 with PSPSC3A / PSPSC2, LDSCDERS) placed by GuardedSpace at O32 with NPROMA blocks
+    that cut the rows: both directions against the oracle, outputs pre-filled with NaN, padding NaN.  Returns (errs, violations)."""
+    to_flat, back = mem
+    nloen = octahedral(nsmax)
+    r = et.setup_trans(nsmax, len(nloen), nloen)
+    try:
+        o = Oracle(nsmax, nloen)
+        ns2, ng = o.nspec2, o.ngptot
+        rng = np.random.default_rng(5)
+        nlev, nvar = 3, 2
+        nsc = 1 + nvar * nlev
+        vor, div = (random_spectrum(rng, o.nasm0, nsmax, ns2, nlev, True) for _ in range(2))
+        sc3 = np.stack([random_spectrum(rng, o.nasm0, nsmax, ns2, nlev, False) for _ in range(nvar)])
+        sc2 = random_spectrum(rng, o.nasm0, nsmax, ns2, 1, False)
+        gref = o.inv_trans(spvor=vor, spdiv=div, spsc=np.concatenate([sc2] + [sc3[v] for v in range(nvar)], axis=1), scders=True)
+        nb = (ng - 1) // nproma + 1
+        assert nb * nproma > ng
+        space = GuardedSpace(lead, guard_for(nloen.max()), to_flat, back)
+        pad = ~(np.arange(nb * nproma) < ng).reshape(nb, nproma)
+        H = lambda v: np.asarray(back(v), dtype=np.float64)
+        flat = lambda a: unblock(a.reshape(nb, -1, nproma), ng)  # (nb, ..., nproma) -> (fields, ngptot)
+        nan = lambda *shape: np.full(shape, np.nan)
+        # ---- INV_TRANS
+        gpuv, gp3a, gp2 = (space.put(nan(*s), "out") for s in ((nb, 2, nlev, nproma), (nb, 3 * nvar, nlev, nproma), (nb, 3, nproma)))
+        et.inv_trans(r, pspvor=space.put(vor, "in"), pspdiv=space.put(div, "in"), pspsc3a=space.put(sc3, "in"), pspsc2=space.put(sc2, "in"),
+                     pgpuv=gpuv, pgp3a=gp3a, pgp2=gp2, ldscders=True, kproma=nproma, mem_space=mem_space)
+        viol = space.check()
+        for nm, a in (("PGPUV", gpuv), ("PGP3A", gp3a), ("PGP2", gp2)):
+            m = np.zeros(tuple(a.shape), dtype=bool)
+            m[...] = pad.reshape((nb,) + (1,) * (len(a.shape) - 2) + (nproma,))
+            viol += space.untouched(a, m, "INV_TRANS call mode 2: padding of " + nm)
+        a3, a2 = flat(H(gp3a)).reshape(3 * nvar, nlev, ng), flat(H(gp2))
+        parts = [np.concatenate([a2[k:k + 1]] + [a3[k * nvar + v] for v in range(nvar)]) for k in range(3)]  # value, N-S, E-W
+        errs = {"inv": _finite_err(np.concatenate([flat(H(gpuv))] + parts), gref, axis=1)}
+        # ---- DIR_TRANS of the oracle's u, v and scalars
+        g = gref[:2 * nlev + nsc]
+        vr, dr, sr = o.dir_trans(g, nuv=nlev, nsc=nsc)
+        blk = lambda x, *mid: block(x, nproma, fill=np.nan).reshape((nb,) + mid + (nproma,))
+        iuv, i3a, i2 = blk(g[:2 * nlev], 2, nlev), blk(g[2 * nlev + 1:], nvar, nlev), blk(g[2 * nlev:2 * nlev + 1], 1)
+        v2, d2, s3, s2 = (space.put(nan(*s), "out") for s in ((ns2, nlev), (ns2, nlev), (nvar, ns2, nlev), (ns2, 1)))
+        et.dir_trans(r, pspvor=v2, pspdiv=d2, pspsc3a=s3, pspsc2=s2, pgpuv=space.put(iuv, "in"), pgp3a=space.put(i3a, "in"),
+                     pgp2=space.put(i2, "in"), kproma=nproma, mem_space=mem_space)
+        viol += space.check()
+        got_sc = np.concatenate([H(s2)] + [H(s3)[v] for v in range(nvar)], axis=1)
+        errs["dir"] = max(_finite_err(H(v2), vr), _finite_err(H(d2), dr), _finite_err(got_sc, sr))
+        return errs, viol
+    finally:
+        et.trans_release(r)
+
+
+def placed_gpnorm_case(et, mem, nsmax=21, nproma=37, nf=4, mem_space=None):
+    """GPNORM_TRANS reads the caller's grid array in place: NaN in the padding of the last NPROMA block and in a surplus field beyond
+    KFIELDS, at lead 0 and 1, against the same call on a plainly allocated array with zeros there (utility_case pins the values).
+    Returns (the largest difference relative to each field's maximum, violations)."""
+    to_flat, back = mem
+    nloen = octahedral(nsmax)
+    r = et.setup_trans(nsmax, len(nloen), nloen)
+    try:
+        ng = et.trans_inq(r, "ngptot")
+        nb = (ng - 1) // nproma + 1
+        assert nb * nproma > ng
+        g = np.random.default_rng(9).uniform(-1, 1, (nf, ng)) + np.arange(nf)[:, None]
+
+        def arr(fill):
+            out = np.full((nb, nf + 1, nproma), fill)
+            out[:, :nf, :] = block(g, nproma, fill=fill)
+            return out
+
+        want = et.gpnorm_trans(r, to_flat(arr(0.0).reshape(-1)).reshape(nb, nf + 1, nproma), kfields=nf, kproma=nproma, mem_space=mem_space)
+        scale = np.abs(g).max(axis=1)
+        err, viol = 0.0, []
+        for lead in (0, 1):
+            space = GuardedSpace(lead, guard_for(nloen.max()), to_flat, back)
+            got = et.gpnorm_trans(r, space.put(arr(np.nan), "in"), kfields=nf, kproma=nproma, mem_space=mem_space)
+            viol += space.check()
+            e = max(float((np.abs(a - b) / scale).max()) for a, b in zip(got, want))
+            err = max(err, e if np.isfinite(e) else np.inf)
+        return err, viol
+    finally:
+        et.trans_release(r)
