@@ -158,6 +158,14 @@ def _bind(L):
         L.emi_esetup.argtypes = [C.POINTER(_ESetup), ip]
         L.emi_einv_trans.argtypes = [C.c_int, C.POINTER(_Inv), C.c_void_p, C.c_void_p]
         L.emi_edir_trans.argtypes = [C.c_int, C.POINTER(_Dir), C.c_void_p, C.c_void_p]
+    if hasattr(L, "emi_especnorm"):  # (an older build loaded for an A/B run)
+        L.emi_especnorm.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, dp]
+        L.emi_especnorm_partial.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, dp]
+        L.emi_egpnorm.argtypes = L.emi_gpnorm.argtypes
+        L.emi_edist_spec.argtypes = L.emi_dist_spec.argtypes
+        L.emi_egath_spec.argtypes = L.emi_gath_spec.argtypes
+        L.emi_edist_grid.argtypes = L.emi_dist_grid.argtypes
+        L.emi_egath_grid.argtypes = L.emi_gath_grid.argtypes
     return L
 
 
@@ -647,6 +655,49 @@ def etrans_inq(kresol, name):
     raise TransError("ETRANS_INQ: unknown quantity %r" % name)
 
 
+def _especnorm_args(kresol, pspec, pmet, mem_space):
+    space = [None, real_dtype(kresol)]
+    if pspec is None or getattr(pspec, "ndim", 0) != 2 or pspec.shape[1] == 0:
+        p, keep, nf = None, None, 0
+        space[0] = EMI_MEM_HOST
+    else:
+        p, keep = _ptr(pspec, space)
+        space[0] = _space(mem_space, space)
+        nf = int(pspec.shape[1])
+    met = None
+    if pmet is not None:  # a small host array, whatever memory the fields live in
+        met = np.ascontiguousarray(_np(pmet), dtype=space[1]).reshape(-1)
+    return space[0], p, nf, met, keep
+
+
+def especnorm(kresol, pspec, pmet=None, mem_space=None):
+    """ESPECNORM (especnorm.h): the spectral norm of every field of pspec (nspec2, nfld) on a handle of ``esetup_trans``, as a
+    numpy array, on every task (the reference: on KMASTER).  PNORM(f)^2 = sum over m, n of w(m, n) (a_r^2 + a_i^2 + b_r^2 + b_i^2);
+    pmet: the metric, a host array read zero-based at NPME(m) + n (etrans_inq "npme"; at least NSPEC2G / 4 + 1 elements, element 0
+    is never read), or None for w = 1.  Several tasks: the library gathers the per-wavenumber sums over the host collectives.
+    mem_space: as ``specnorm``."""
+    space, p, nf, met, keep = _especnorm_args(kresol, pspec, pmet, mem_space)
+    out = np.zeros(nf)
+    _chk(lib().emi_especnorm(kresol, space, p, nf, None if met is None else met.ctypes.data, 0 if met is None else met.size,
+                             out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def especnorm_partial(kresol, pspec, pmet=None, mem_space=None):
+    """emi_especnorm_partial: (nump, nfld) sums S(f, m) of this task's x-wavenumbers, in MYMS order; arguments as ``especnorm``."""
+    space, p, nf, met, keep = _especnorm_args(kresol, pspec, pmet, mem_space)
+    out = np.zeros((trans_inq(kresol, "nump"), nf))
+    _chk(lib().emi_especnorm_partial(kresol, space, p, nf, None if met is None else met.ctypes.data, 0 if met is None else met.size,
+                                     out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def egpnorm_trans(kresol, pgp, kfields=None, kproma=None, ldave_only=False, pmin=None, pmax=None, mem_space=None):
+    """EGPNORM_TRANS (egpnorm_trans.h): (PAVE, PMIN, PMAX) as ``gpnorm_trans`` on a handle of ``esetup_trans``: the average over all
+    NDGL x NDLON points, extension zone included, each row weighted 1 / NDGL."""
+    return _gpnorm("emi_egpnorm", kresol, pgp, kfields, kproma, ldave_only, pmin, pmax, mem_space)
+
+
 def specnorm(kresol, pspec, kvset=None, mem_space=None):
     """SPECNORM (specnorm.h:12): per-field spectral L2 norm, returned as a numpy array (on every
     task; the reference returns it on the master only).  kvset (NPRTRV > 1, specnorm.F90:82-101): V-set of every GLOBAL
@@ -681,6 +732,11 @@ def gpnorm_trans(kresol, pgp, kfields=None, kproma=None, ldave_only=False, pmin=
     reference: task 1).  ldave_only: pmin / pmax are the caller's local extrema and are only reduced over the tasks.
     mem_space: overrides the memory space derived from the arrays (EMI_MEM_AUTO; on the CPU emulator of the tests EMI_MEM_DEVICE uses
     numpy arrays in place, the path device tensors take on a GPU)."""
+    return _gpnorm("emi_gpnorm", kresol, pgp, kfields, kproma, ldave_only, pmin, pmax, mem_space)
+
+
+def _gpnorm(fn, kresol, pgp, kfields, kproma, ldave_only, pmin, pmax, mem_space):
+    """gpnorm_trans / egpnorm_trans over the entry point `fn`"""
     space = [None, real_dtype(kresol)]
     p, keep = _ptr(pgp, space)
     space[0] = _space(mem_space, space)
@@ -692,7 +748,7 @@ def gpnorm_trans(kresol, pgp, kfields=None, kproma=None, ldave_only=False, pmin=
     if ldave_only:
         mn[:], mx[:] = np.asarray(pmin, dtype=np.float64)[:nf], np.asarray(pmax, dtype=np.float64)[:nf]
     pd = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-    _chk(lib().emi_gpnorm(kresol, space[0], p, int(pgp.shape[1]), nf, nproma, pd(ave), pd(mn), pd(mx), int(bool(ldave_only))))
+    _chk(getattr(lib(), fn)(kresol, space[0], p, int(pgp.shape[1]), nf, nproma, pd(ave), pd(mn), pd(mx), int(bool(ldave_only))))
     return ave, mn, mx
 
 
@@ -750,66 +806,120 @@ def dist_spec(kresol, pspecg, kfdistg, kfrom=1):
     """DIST_SPEC (dist_spec.h:11) over emi_dist_spec: global spectral fields `pspecg` (nspec2g, kfdistg), field f held
     by task kfrom[f] (1-based; the columns of other tasks' fields are not read, the array may be None on a task that is
     the source of none), -> this task's (nspec2, kfdistg) local array."""
+    return _dist_spec("", kresol, pspecg, kfdistg, kfrom, None)
+
+
+def _dist_spec(_e, kresol, pspecg, kfdistg, kfrom, ksort):
+    """dist_spec (_e = "") / edist_spec (_e = "e")"""
     dt = real_dtype(kresol)
     ns2g, ns2, me = trans_inq(kresol, "nspec2g"), trans_inq(kresol, "nspec2"), trans_inq(kresol, "myproc")
-    kfrom = _roots(kfrom, kfdistg, "DIST_SPEC:KFROM")
+    who = _e.upper() + "DIST_SPEC"
+    kfrom = _roots(kfrom, kfdistg, who + ":KFROM")
     mine = np.flatnonzero(kfrom == me)
     g = None
     if mine.size:
         a = _np(pspecg)
         if a.shape[0] != ns2g:
-            raise TransError("DIST_SPEC: PSPECG must have shape (nspec2g=%d, nfld)" % ns2g)
+            raise TransError("%s: PSPECG must have shape (nspec2g=%d, nfld)" % (who, ns2g))
         g = np.ascontiguousarray(a[:, mine].T, dtype=dt)  # [n_mine][nspec2g]
     out = np.zeros((ns2, kfdistg), dtype=dt)
-    _chk(lib().emi_dist_spec(kresol, None if g is None else g.ctypes.data, kfdistg, _iptr(kfrom), None, out.ctypes.data))
+    ks = None if ksort is None else np.ascontiguousarray(ksort, dtype=np.int32)
+    _chk(getattr(lib(), "emi_%sdist_spec" % _e)(kresol, None if g is None else g.ctypes.data, kfdistg, _iptr(kfrom),
+                                                None if ks is None else _iptr(ks), out.ctypes.data))
     return out
 
 
 def gath_spec(kresol, pspec, kfgathg, kto=1):
     """GATH_SPEC (gath_spec.h:11) over emi_gath_spec: local (nspec2, kfgathg) -> global (nspec2g, n_mine) holding the
     fields this task is the target of (None if it is the target of none)."""
+    return _gath_spec("", kresol, pspec, kfgathg, kto)
+
+
+def _gath_spec(_e, kresol, pspec, kfgathg, kto):
+    """gath_spec (_e = "") / egath_spec (_e = "e")"""
     dt = real_dtype(kresol)
     ns2g, me = trans_inq(kresol, "nspec2g"), trans_inq(kresol, "myproc")
-    kto = _roots(kto, kfgathg, "GATH_SPEC:KTO")
+    kto = _roots(kto, kfgathg, _e.upper() + "GATH_SPEC:KTO")
     loc = np.ascontiguousarray(_np(pspec), dtype=dt)
     nm = int((kto == me).sum())
     g = np.zeros((nm, ns2g), dtype=dt) if nm else None
-    _chk(lib().emi_gath_spec(kresol, None if g is None else g.ctypes.data, kfgathg, _iptr(kto), loc.ctypes.data))
+    _chk(getattr(lib(), "emi_%sgath_spec" % _e)(kresol, None if g is None else g.ctypes.data, kfgathg, _iptr(kto), loc.ctypes.data))
     return None if g is None else np.ascontiguousarray(g.T)
 
 
 def gath_grid(kresol, pgp, kfgathg, kto=1):
     """GATH_GRID (gath_grid.h:11) over emi_gath_grid: local blocked grid array (ngpblks, kfgathg, nproma) -> global
     (n_mine, ngptotg) of the fields this task is the target of (None if none)."""
+    return _gath_grid("", kresol, pgp, kfgathg, kto)
+
+
+def _gath_grid(_e, kresol, pgp, kfgathg, kto):
+    """gath_grid (_e = "") / egath_grid (_e = "e")"""
     dt = real_dtype(kresol)
     ngg, me = trans_inq(kresol, "ngptotg"), trans_inq(kresol, "myproc")
-    kto = _roots(kto, kfgathg, "GATH_GRID:KTO")
+    who = _e.upper() + "GATH_GRID"
+    kto = _roots(kto, kfgathg, who + ":KTO")
     loc = np.ascontiguousarray(_np(pgp), dtype=dt)
     if loc.ndim != 3 or loc.shape[1] != kfgathg:
-        raise TransError("GATH_GRID: PGP must have shape (ngpblks, kfgathg=%d, nproma)" % kfgathg)
+        raise TransError("%s: PGP must have shape (ngpblks, kfgathg=%d, nproma)" % (who, kfgathg))
     nm = int((kto == me).sum())
     g = np.zeros((nm, ngg), dtype=dt) if nm else None
-    _chk(lib().emi_gath_grid(kresol, None if g is None else g.ctypes.data, kfgathg, _iptr(kto), loc.shape[2], loc.ctypes.data))
+    _chk(getattr(lib(), "emi_%sgath_grid" % _e)(kresol, None if g is None else g.ctypes.data, kfgathg, _iptr(kto), loc.shape[2], loc.ctypes.data))
     return g
 
 
 def dist_grid(kresol, pgpg, kfdistg, kfrom=1, kproma=None):
     """DIST_GRID (dist_grid.h:11) over emi_dist_grid: global (kfdistg, ngptotg) on task kfrom[f] -> this task's blocked
     (ngpblks, kfdistg, nproma) array (padding of the last block zero)."""
+    return _dist_grid("", kresol, pgpg, kfdistg, kfrom, kproma, None)
+
+
+def _dist_grid(_e, kresol, pgpg, kfdistg, kfrom, kproma, ksort):
+    """dist_grid (_e = "") / edist_grid (_e = "e")"""
     dt = real_dtype(kresol)
     ngl, ngg, me = trans_inq(kresol, "ngptot"), trans_inq(kresol, "ngptotg"), trans_inq(kresol, "myproc")
-    kfrom = _roots(kfrom, kfdistg, "DIST_GRID:KFROM")
+    who = _e.upper() + "DIST_GRID"
+    kfrom = _roots(kfrom, kfdistg, who + ":KFROM")
     mine = np.flatnonzero(kfrom == me)
     g = None
     if mine.size:
         a = _np(pgpg)
         if a.shape[-1] != ngg:
-            raise TransError("DIST_GRID: PGPG must have shape (nfld, ngptotg=%d)" % ngg)
+            raise TransError("%s: PGPG must have shape (nfld, ngptotg=%d)" % (who, ngg))
         g = np.ascontiguousarray(a[mine], dtype=dt)
     nproma = int(kproma) if kproma else ngl
     out = np.zeros(((ngl - 1) // nproma + 1, kfdistg, nproma), dtype=dt)
-    _chk(lib().emi_dist_grid(kresol, None if g is None else g.ctypes.data, kfdistg, _iptr(kfrom), None, nproma, out.ctypes.data))
+    ks = None if ksort is None else np.ascontiguousarray(ksort, dtype=np.int32)
+    _chk(getattr(lib(), "emi_%sdist_grid" % _e)(kresol, None if g is None else g.ctypes.data, kfdistg, _iptr(kfrom),
+                                                None if ks is None else _iptr(ks), nproma, out.ctypes.data))
     return out
+
+
+def edist_spec(kresol, pspecg, kfdistg, kfrom=1, ksort=None):
+    """EDIST_SPEC (edist_spec.h): ``dist_spec`` on a handle of ``esetup_trans``.  A global spectral field is the one-task layout:
+    m = 0 .. KMSMAX ascending, 4 (KNTMP(m) + 1) reals each.  ksort: field f lands in column ksort[f] (1-based) of the result."""
+    return _dist_spec("e", kresol, pspecg, kfdistg, kfrom, ksort)
+
+
+def egath_spec(kresol, pspec, kfgathg, kto=1, ksmax=None, kmsmax=None, ldza0ip=False):
+    """EGATH_SPEC (egath_spec.h): ``gath_spec`` on a handle of ``esetup_trans``.  The whole spectrum only: ksmax / kmsmax are accepted
+    where they equal the handle's, and ldza0ip, which addresses the spherical layout, is refused."""
+    if (ksmax is not None and int(ksmax) != etrans_inq(kresol, "nsmax")) or (kmsmax is not None and int(kmsmax) != etrans_inq(kresol, "nmsmax")):
+        raise TransError("EGATH_SPEC: KSMAX / KMSMAX (truncated gather) not supported")
+    if ldza0ip:
+        raise TransError("EGATH_SPEC: LDZA0IP not supported")
+    return _gath_spec("e", kresol, pspec, kfgathg, kto)
+
+
+def edist_grid(kresol, pgpg, kfdistg, kfrom=1, kproma=None, ksort=None):
+    """EDIST_GRID (edist_grid.h): ``dist_grid`` on a handle of ``esetup_trans``.  A global grid field is the NDGL x NDLON points row
+    after row.  ksort: field f lands in slot ksort[f] (1-based) of the result."""
+    return _dist_grid("e", kresol, pgpg, kfdistg, kfrom, kproma, ksort)
+
+
+def egath_grid(kresol, pgp, kfgathg, kto=1):
+    """EGATH_GRID (egath_grid.h): ``gath_grid`` on a handle of ``esetup_trans``."""
+    return _gath_grid("e", kresol, pgp, kfgathg, kto)
 
 
 def trans_release(kresol):

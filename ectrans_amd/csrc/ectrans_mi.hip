@@ -298,6 +298,8 @@ struct Plan {  // owns its device memory; whoever drops a plan that has run some
   double exwn = 0.0, eywn = 0.0;
   std::vector<int> kntmp;           // [KMSMAX + 1] the ellipse (ellips.F90:71-97)
   std::vector<int> l_kntmp, nesm0;  // [nump] of the local wavenumbers; nesm0 0-based
+  std::vector<int> l_npme;          // [nump] NPME of the local wavenumbers: zero-based position of (m, n = 0) in PMET (ESPECNORM)
+  const int *d_npme = nullptr;
   LamDev lamdev{};
   int lam_nthr = 0;
   size_t lam_lds = 0;
@@ -1719,6 +1721,11 @@ extern "C" int emi_esetup(const emi_esetup_t *cfg, int *kresol) {
     ipos += 4 * (P.kntmp[P.mval[ml]] + 1);
   }
   P.nspec2 = ipos;
+  {  // NPME(0) = 1, NPME(m) = NPME(m - 1) + KNTMP(m - 1) + 1 (suemp_trans_preleg_mod.F90:75-86)
+    std::vector<int> npme(M + 1, 1);
+    for (int m = 1; m <= M; m++) npme[m] = npme[m - 1] + P.kntmp[m - 1] + 1;
+    for (int ml = 0; ml < NU; ml++) P.l_npme.push_back(npme[P.mval[ml]]);
+  }
   P.lbase.assign(NU + 1, 0);  // no hemispheres: the row tables of the y-side are lamdev.rowbase
   P.l_nmen.assign(NL, M);
   P.l_gpoff.assign(NL, 0);
@@ -1749,7 +1756,7 @@ extern "C" int emi_esetup(const emi_esetup_t *cfg, int *kresol) {
   if (upload(P.dev_allocs, P.mval, &g.mval) || upload(P.dev_allocs, P.l_nmen, &g.nmen) || upload(P.dev_allocs, P.l_gpoff, &g.gpoff) ||
       upload(P.dev_allocs, P.l_fbase, &g.fbase) || upload(P.dev_allocs, T.fftrow, &g.fftrow) || upload(P.dev_allocs, T.l_rw, &g.rw) ||
       upload(P.dev_allocs, T.l_racthe, &g.racthe) || upload(P.dev_allocs, P.l_kntmp, &ld.kntmp) || upload(P.dev_allocs, P.nesm0, &ld.nesm0) ||
-      upload(P.dev_allocs, rowbase, &ld.rowbase))
+      upload(P.dev_allocs, rowbase, &ld.rowbase) || upload(P.dev_allocs, P.l_npme, &P.d_npme))
     return EMI_ERR_RUNTIME;
   if (!T.rowtable) g.fftrow = nullptr;
   if ((rc = build_fft_plans(P))) return rc;
@@ -3306,23 +3313,92 @@ extern "C" int emi_specnorm_partial(int kresol, int mem_space, const void *spec,
   return specnorm_sumsq(*Pp, mem_space, spec, nfld, sumsq);
 }
 
+// ESPECNORM (etrans/cpu/external/especnorm.F90, internal/espnorm_ctl_mod.F90, espnormd_mod.F90): the spectral norms of a limited-area
+// handle.  sums[ml][f], ml over this task's wavenumbers in MYMS order: k_especnorm.  pmet: host array of the handle's precision, read
+// zero-based at NPME(m) + n (element 0 is never read), or NULL for weights of 1; it is small and is uploaded with every call.
+static int especnorm_check(const char *who, int kresol, const void *spec, int nfld, const void *pmet, int npmet, const void *out, Plan **Pp) {
+  Plan *P = get_plan(kresol);
+  if (!P) EMI_FAIL(EMI_ERR_STATE, "%s: unknown resolution %d", who, kresol);
+  if (!P->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is not a limited-area handle: it was not set up by ESETUP_TRANS", who, kresol);
+  if (nfld <= 0 || !spec) EMI_FAIL(EMI_ERR_ARG, "ESPECNORM: PSPEC NOT PRESENT");
+  if (!out) EMI_FAIL(EMI_ERR_ARG, "ESPECNORM: PNORM NOT PRESENT");
+  if (pmet && npmet < 1 + P->nspec2g / 4)  // NPME(KMSMAX) + KNTMP(KMSMAX) + 1
+    EMI_FAIL(EMI_ERR_ARG, "ESPECNORM: PMET TOO SMALL (%d elements, %d are needed)", npmet, 1 + P->nspec2g / 4);
+  *Pp = P;
+  return 0;
+}
+static int especnorm_sums(Plan &P, int mem_space, const void *spec, int nfld, const void *pmet, int npmet, double *sums) {
+  if (resolve_space("ESPECNORM", mem_space, {spec}, &mem_space)) return EMI_ERR_ARG;
+  if (P.nump == 0) return EMI_SUCCESS;
+  HostStage hs(P.esz);
+  if (plan_begin(P, (emi_stream_t)0)) return EMI_ERR_RUNTIME;  // the null stream, behind the last transform of this resolution (SPECNORM)
+  const void *d_sp = hs.in(spec, (size_t)P.nspec2 * nfld, mem_space == EMI_MEM_HOST, 0);
+  if (hs.failed) EMI_FAIL(EMI_ERR_RUNTIME, "ESPECNORM: cannot stage the host array through device memory");
+  void *d_out = nullptr, *d_met = nullptr;
+  const size_t nout = (size_t)P.nump * nfld;
+  int rc = EMI_SUCCESS;
+  if (emi_dev_malloc(&d_out, nout * 8) || (pmet && (emi_dev_malloc(&d_met, (size_t)npmet * P.esz) || emi_h2d(d_met, pmet, (size_t)npmet * P.esz, 0)))) {
+    rc = EMI_ERR_RUNTIME;
+  } else {
+    const int ntile = (nfld + 63) / 64;
+    EMI_LAUNCH_P(P.esz, k_especnorm, (long long)P.nump * ntile, 256, 3 * 64 * 8, (emi_stream_t)0, P.lamdev.kntmp, P.lamdev.nesm0, P.d_npme, ntile, (const RT *)d_sp, nfld,
+                 (const RT *)d_met, (double *)d_out);
+    if (emi_d2h(sums, d_out, nout * 8, 0)) rc = EMI_ERR_RUNTIME;
+  }
+  if (emi_stream_sync(0)) rc = EMI_ERR_RUNTIME;  // (also: the caller's pmet has been read)
+  emi_dev_free(d_out);
+  emi_dev_free(d_met);
+  return rc;
+}
+extern "C" int emi_especnorm_partial(int kresol, int mem_space, const void *spec, int nfld, const void *pmet, int npmet, double *sums) {
+  Plan *Pp = nullptr;
+  if (int rc = especnorm_check("ESPECNORM", kresol, spec, nfld, pmet, npmet, sums, &Pp)) return rc;
+  return especnorm_sums(*Pp, mem_space, spec, nfld, pmet, npmet, sums);
+}
+// The per-wavenumber sums of all tasks are gathered (SPNORMC) and added for m = 0 .. KMSMAX in ascending order on every task, the
+// reference's SUM(ZGM,DIM=2) (espnorm_ctl_mod.F90:64-69): the norms do not depend on the number of tasks, and every task gets them.
+extern "C" int emi_especnorm(int kresol, int mem_space, const void *spec, int nfld, const void *pmet, int npmet, double *norms) {
+  Plan *Pp = nullptr;
+  if (int rc = especnorm_check("ESPECNORM", kresol, spec, nfld, pmet, npmet, norms, &Pp)) return rc;
+  Plan &P = *Pp;
+  const int NP = P.nproc, M = P.nsmax;
+  if (NP > 1 && !G.hc_gather)
+    EMI_FAIL(EMI_ERR_STATE, "ESPECNORM: several tasks and no host collectives (emi_set_host_collectives): use emi_especnorm_partial and gather the sums");
+  std::vector<double> mine((size_t)std::max(P.nump, 1) * nfld, 0.0), all;
+  if (int rc = especnorm_sums(P, mem_space, spec, nfld, pmet, npmet, mine.data())) return rc;
+  std::vector<long long> cnt(NP, 0), dsp(NP, 0);
+  std::vector<int> lidx(M + 1, 0), numpp(NP, 0);
+  for (int m = 0; m <= M; m++) lidx[m] = numpp[P.procm[m]]++;
+  const double *base = mine.data();
+  if (NP > 1) {
+    long long tot = 0;
+    for (int t = 0; t < NP; t++) cnt[t] = 8LL * numpp[t] * nfld, dsp[t] = tot, tot += cnt[t];
+    all.resize((size_t)(tot / 8));
+    if (G.hc_gather(G.hc_user, mine.data(), cnt[P.me], all.data(), cnt.data(), dsp.data(), NP)) EMI_FAIL(EMI_ERR_RUNTIME, "ESPECNORM: all-gather-v failed");
+    base = all.data();
+  }
+  for (int f = 0; f < nfld; f++) {
+    double s = 0.0;
+    for (int m = 0; m <= M; m++) s += base[(size_t)(dsp[P.procm[m]] / 8) + (size_t)lidx[m] * nfld + f];
+    norms[f] = std::sqrt(s);
+  }
+  return EMI_SUCCESS;
+}
+
 // GPNORM_TRANS (cpu/external/gpnorm_trans.F90:11-96, cpu/internal/gpnorm_trans_ctl_mod.F90): area-weighted average, minimum and maximum of
 // `kfields` grid fields of PGP(nproma, gp_nfld, ngpblks).  Per latitude the sum over the longitudes in double times RW / NLOEN on the
 // task that holds the latitude (whole latitudes here, so the reference's TRGTOL is not needed); the per-latitude values of all tasks
 // are gathered and summed in latitude order on every task (the reference: on task 1), so the average does not depend on the
 // decomposition.  ave_only (LDAVE_ONLY): pmin / pmax come in as the caller's local extrema and are only reduced over the tasks.
 // Host arrays are staged whole (all gp_nfld fields of PGP, although only the first kfields are reduced): a diagnostic, not a hot path.
-extern "C" int emi_gpnorm(int kresol, int mem_space, const void *gp, int gp_nfld, int kfields, int kproma, double *ave, double *pmin, double *pmax,
-                          int ave_only) {
-  Plan *Pp = get_plan(kresol);
-  if (!Pp) EMI_FAIL(EMI_ERR_STATE, "GPNORM_TRANS: unknown resolution %d", kresol);
-  if (Pp->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): this routine serves the spherical transforms only", "GPNORM_TRANS", kresol);
-  Plan &P = *Pp;
-  if (P.ldll) EMI_FAIL(EMI_ERR_UNSUPPORTED, "GPNORM_TRANS: not available on a handle set up with LDLL (it keeps no Gaussian weights)");
-  if (kfields <= 0 || !gp || !ave || !pmin || !pmax) EMI_FAIL(EMI_ERR_ARG, "GPNORM_TRANS: bad arguments");
+// The rows, their weights RW and their lengths come from the plan: Gaussian latitudes and weights (GPNORM_TRANS), or the NDGL rows of a
+// limited-area handle, extension zone included, with RW = 1 / NDGL (EGPNORM_TRANS, etrans/cpu/external/egpnorm_trans.F90:94-97).
+static int gpnorm_impl(Plan &P, const char *who, int mem_space, const void *gp, int gp_nfld, int kfields, int kproma, double *ave, double *pmin, double *pmax,
+                       int ave_only) {
+  if (kfields <= 0 || !gp || !ave || !pmin || !pmax) EMI_FAIL(EMI_ERR_ARG, "%s: bad arguments", who);
   if (gp_nfld < kfields) EMI_FAIL(EMI_ERR_ARG, "GPNORM_TRANS_CTL:SECOND DIMENSION OF PGP TOO SMALL (%d < %d)", gp_nfld, kfields);
-  if (G.nproc_all > 1 && !G.hc_gather) EMI_FAIL(EMI_ERR_STATE, "GPNORM_TRANS: several tasks and no host collectives (emi_set_host_collectives)");
-  if (resolve_space("GPNORM_TRANS", mem_space, {gp}, &mem_space)) return EMI_ERR_ARG;
+  if (G.nproc_all > 1 && !G.hc_gather) EMI_FAIL(EMI_ERR_STATE, "%s: several tasks and no host collectives (emi_set_host_collectives)", who);
+  if (resolve_space(who, mem_space, {gp}, &mem_space)) return EMI_ERR_ARG;
   const int j0 = P.vfirst(P.me, P.mev), j1 = P.vlast(P.me, P.mev), nl = j1 - j0;
   std::vector<int> rowoff(nl + 1, 0);
   for (int j = 0; j < nl; j++) rowoff[j + 1] = rowoff[j] + P.nloen[j0 + j];
@@ -3377,14 +3453,14 @@ extern "C" int emi_gpnorm(int kresol, int mem_space, const void *gp, int gp_nfld
         cnt[t] = 8LL * ((long long)kfields * nlat_of[t] + 2 * kfields + 1), dsp[t] = tot, tot += cnt[t];
       }
     all.resize((size_t)(tot / 8));
-    if (G.hc_gather(G.hc_user, blk.data(), cnt[G.myproc_all - 1], all.data(), cnt.data(), dsp.data(), NA)) EMI_FAIL(EMI_ERR_RUNTIME, "GPNORM_TRANS: all-gather-v failed");
+    if (G.hc_gather(G.hc_user, blk.data(), cnt[G.myproc_all - 1], all.data(), cnt.data(), dsp.data(), NA)) EMI_FAIL(EMI_ERR_RUNTIME, "%s: all-gather-v failed", who);
   } else {
     nlat_of[0] = nl, cnt[0] = 8LL * (long long)blk.size();
     all = blk;
   }
   for (int t = 0; t < NA; t++)
     if (all[(size_t)(dsp[t] / 8) + (size_t)kfields * nlat_of[t] + 2 * (size_t)kfields] != 0.0)
-      EMI_FAIL(EMI_ERR_RUNTIME, "GPNORM_TRANS: task %d could not stage or reduce its fields (no device memory?)", t + 1);
+      EMI_FAIL(EMI_ERR_RUNTIME, "%s: task %d could not stage or reduce its fields (no device memory?)", who, t + 1);
   for (int f = 0; f < kfields; f++) {  // latitude order = task order (bands and sub-bands ascend with the task number)
     double a = 0.0, mn = 0.0, mx = 0.0;
     bool first = true;
@@ -3400,6 +3476,23 @@ extern "C" int emi_gpnorm(int kresol, int mem_space, const void *gp, int gp_nfld
     ave[f] = a, pmin[f] = mn, pmax[f] = mx;
   }
   return EMI_SUCCESS;
+}
+
+extern "C" int emi_gpnorm(int kresol, int mem_space, const void *gp, int gp_nfld, int kfields, int kproma, double *ave, double *pmin, double *pmax,
+                          int ave_only) {
+  Plan *Pp = get_plan(kresol);
+  if (!Pp) EMI_FAIL(EMI_ERR_STATE, "GPNORM_TRANS: unknown resolution %d", kresol);
+  if (Pp->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): this routine serves the spherical transforms only", "GPNORM_TRANS", kresol);
+  if (Pp->ldll) EMI_FAIL(EMI_ERR_UNSUPPORTED, "GPNORM_TRANS: not available on a handle set up with LDLL (it keeps no Gaussian weights)");
+  return gpnorm_impl(*Pp, "GPNORM_TRANS", mem_space, gp, gp_nfld, kfields, kproma, ave, pmin, pmax, ave_only);
+}
+// EGPNORM_TRANS: PAVE = sum over all NDGL rows of (1 / NDGL) (row sum) / NDLON; the reference's EGPNORM_OLD variant is not provided
+extern "C" int emi_egpnorm(int kresol, int mem_space, const void *gp, int gp_nfld, int kfields, int kproma, double *ave, double *pmin, double *pmax,
+                           int ave_only) {
+  Plan *Pp = get_plan(kresol);
+  if (!Pp) EMI_FAIL(EMI_ERR_STATE, "EGPNORM_TRANS: unknown resolution %d", kresol);
+  if (!Pp->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is not a limited-area handle: it was not set up by ESETUP_TRANS", "EGPNORM_TRANS", kresol);
+  return gpnorm_impl(*Pp, "EGPNORM_TRANS", mem_space, gp, gp_nfld, kfields, kproma, ave, pmin, pmax, ave_only);
 }
 
 // VORDIV_TO_UV (cpu/external/vordiv_to_uv.F90:11-178): spectral vorticity / divergence -> spectral U = u cos(theta), V = v cos(theta), for the
@@ -3557,6 +3650,7 @@ extern "C" int emi_inq_tasks(int *nproc, int *myproc) {
 namespace {
 struct TaskLayout {  // global <-> per-task positions of one resolution
   std::vector<long long> iasm0g;              // [N+1] global start of wavenumber m
+  std::vector<long long> mlen;                // [N+1] reals of wavenumber m: 2 (NSMAX - m + 1), or 4 (KNTMP(m) + 1) on a limited-area handle
   std::vector<std::vector<int>> ms;           // [task] its wavenumbers, ascending
   std::vector<std::vector<long long>> start;  // [task][i] local start of ms[task][i]
   std::vector<long long> nspec2, gp0, ngp;    // [task]
@@ -3565,7 +3659,11 @@ TaskLayout task_layout(const Plan &P) {
   TaskLayout L;
   const int N = P.nsmax, NP = P.nproc;
   L.iasm0g.assign(N + 2, 0);
-  for (int m = 0; m <= N; m++) L.iasm0g[m + 1] = L.iasm0g[m] + 2LL * (N - m + 1);
+  L.mlen.assign(N + 1, 0);
+  for (int m = 0; m <= N; m++) {  // (a limited-area handle: N = KMSMAX; the global field is the one-task layout, NCPL4M(m) reals per m)
+    L.mlen[m] = P.lam ? 4LL * (P.kntmp[m] + 1) : 2LL * (N - m + 1);
+    L.iasm0g[m + 1] = L.iasm0g[m] + L.mlen[m];
+  }
   L.ms.assign(NP, {});
   L.start.assign(NP, {});
   L.nspec2.assign(NP, 0);
@@ -3573,7 +3671,7 @@ TaskLayout task_layout(const Plan &P) {
     const int t = P.procm[m];
     L.ms[t].push_back(m);
     L.start[t].push_back(L.nspec2[t]);
-    L.nspec2[t] += 2LL * (N - m + 1);
+    L.nspec2[t] += L.mlen[m];
   }
   std::vector<long long> cum(P.ndgl + 1, 0);
   for (int j = 0; j < P.ndgl; j++) cum[j + 1] = cum[j] + P.nloen[j];
@@ -3606,10 +3704,11 @@ int slot_of(const int *ksort, int f, int nfld, const char *who, int *slot) {
 
 // global fields on their source tasks -> every task's share.  One broadcast per source task.
 template <bool SPEC>
-static int dist_impl(int kresol, const void *glob, int nfld, const int *kfrom, const int *ksort, int kproma, void *loc, const char *who) {
+static int dist_impl(int kresol, const void *glob, int nfld, const int *kfrom, const int *ksort, int kproma, void *loc, const char *who, bool lam = false) {
   Plan *Pp = get_plan(kresol);
   if (!Pp) EMI_FAIL(EMI_ERR_STATE, "%s: unknown resolution %d", who, kresol);
-  if (Pp->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): this routine serves the spherical transforms only", who, kresol);
+  if (Pp->lam && !lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): this routine serves the spherical transforms only", who, kresol);
+  if (!Pp->lam && lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is not a limited-area handle: it was not set up by ESETUP_TRANS", who, kresol);
   Plan &P = *Pp;
   if (check_tasks(P, kfrom, nfld, who)) return EMI_ERR_ARG;
   if (!loc) EMI_FAIL(EMI_ERR_ARG, "%s: local array missing", who);
@@ -3643,7 +3742,7 @@ static int dist_impl(int kresol, const void *glob, int nfld, const int *kfrom, c
       if (SPEC) {  // PSPEC(nfld, nspec2): element (slot, isp)
         const std::vector<int> &ms = L.ms[P.me];
         for (size_t k = 0; k < ms.size(); k++) {
-          const long long cnt = 2LL * (P.nsmax - ms[k] + 1), gs = L.iasm0g[ms[k]], ls = L.start[P.me][k];
+          const long long cnt = L.mlen[ms[k]], gs = L.iasm0g[ms[k]], ls = L.start[P.me][k];
           for (long long e = 0; e < cnt; e++) memcpy((char *)loc + ((size_t)(ls + e) * nfld + slot) * esz, g + (size_t)(gs + e) * esz, esz);
         }
       } else {  // PGP(nproma, nfld, ngpblks): point p -> block p / nproma
@@ -3660,10 +3759,11 @@ static int dist_impl(int kresol, const void *glob, int nfld, const int *kfrom, c
 
 // every task's share -> global fields on their target tasks.  An all-gather-v of the packed local fields per chunk of fields.
 template <bool SPEC>
-static int gath_impl(int kresol, void *glob, int nfld, const int *kto, int kproma, const void *loc, const char *who) {
+static int gath_impl(int kresol, void *glob, int nfld, const int *kto, int kproma, const void *loc, const char *who, bool lam = false) {
   Plan *Pp = get_plan(kresol);
   if (!Pp) EMI_FAIL(EMI_ERR_STATE, "%s: unknown resolution %d", who, kresol);
-  if (Pp->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): this routine serves the spherical transforms only", who, kresol);
+  if (Pp->lam && !lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): this routine serves the spherical transforms only", who, kresol);
+  if (!Pp->lam && lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is not a limited-area handle: it was not set up by ESETUP_TRANS", who, kresol);
   Plan &P = *Pp;
   if (check_tasks(P, kto, nfld, who)) return EMI_ERR_ARG;
   if (!loc) EMI_FAIL(EMI_ERR_ARG, "%s: local array missing", who);
@@ -3720,7 +3820,7 @@ static int gath_impl(int kresol, void *glob, int nfld, const int *kto, int kprom
         const char *src = base + dsp[t] + (size_t)fc * nloc(t) * esz;
         if (SPEC) {
           for (size_t k = 0; k < L.ms[t].size(); k++) {
-            const long long cnte = 2LL * (P.nsmax - L.ms[t][k] + 1);
+            const long long cnte = L.mlen[L.ms[t][k]];
             memcpy(g + (size_t)L.iasm0g[L.ms[t][k]] * esz, src + (size_t)L.start[t][k] * esz, (size_t)cnte * esz);
           }
         } else {
@@ -3743,6 +3843,21 @@ extern "C" int emi_dist_grid(int kresol, const void *gpg, int nfld, const int *k
 }
 extern "C" int emi_gath_grid(int kresol, void *gpg, int nfld, const int *kto, int kproma, const void *gp) {
   return gath_impl<false>(kresol, gpg, nfld, kto, kproma, gp, "GATH_GRID");
+}
+// EDIST_SPEC / EGATH_SPEC / EDIST_GRID / EGATH_GRID: the same on a limited-area handle.  A global spectral field is the one-task layout,
+// m = 0 .. KMSMAX ascending with 4 (KNTMP(m) + 1) reals each (gath_spec_control_mod.F90:108-113 with KN = NCPL4M); a global grid field
+// the NDGL x NDLON points row after row, the tasks' bands of whole rows in task order.
+extern "C" int emi_edist_spec(int kresol, const void *specg, int nfld, const int *kfrom, const int *ksort, void *spec) {
+  return dist_impl<true>(kresol, specg, nfld, kfrom, ksort, 0, spec, "EDIST_SPEC", true);
+}
+extern "C" int emi_egath_spec(int kresol, void *specg, int nfld, const int *kto, const void *spec) {
+  return gath_impl<true>(kresol, specg, nfld, kto, 0, spec, "EGATH_SPEC", true);
+}
+extern "C" int emi_edist_grid(int kresol, const void *gpg, int nfld, const int *kfrom, const int *ksort, int kproma, void *gp) {
+  return dist_impl<false>(kresol, gpg, nfld, kfrom, ksort, kproma, gp, "EDIST_GRID", true);
+}
+extern "C" int emi_egath_grid(int kresol, void *gpg, int nfld, const int *kto, int kproma, const void *gp) {
+  return gath_impl<false>(kresol, gpg, nfld, kto, kproma, gp, "EGATH_GRID", true);
 }
 
 // CRC-64/ECMA-182, table driven (ectrans-benchmark.F90:1455-1600 calls fiat's crc64, un-vendored)

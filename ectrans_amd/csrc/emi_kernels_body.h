@@ -3221,6 +3221,57 @@ EMI_KERNEL_LB(256) void k_gpnorm(const int *rowoff /* [nlat + 1] first local poi
 }
 
 // ==========================================================================================
+// k_especnorm: ESPNORMD (etrans espnormd_mod.F90:40-57) of a limited-area handle: for local x-wavenumber ml and field f
+//   out[ml][f] = sum over n = 0 .. KNTMP(m) of PMET(NPME(m) + n) (a_r^2 + a_i^2 + b_r^2 + b_i^2),
+// the four reals of (m, n) at NESM0(m) + 4 n of PSPEC(nfld, nspec2); pmet (zero-based, NULL: weights 1) and the inputs convert to
+// double exactly, every sum is in double.  One workgroup of 256 threads per (ml, tile of 64 fields), lane = field: a wave reads rows
+// of 64 consecutive reals.  Wave w walks n in [w K / 4, (w + 1) K / 4), K = KNTMP(m) + 1, in ascending order, four n (16 row loads)
+// in flight; the four partial sums are added in wave order.  The summation tree of one (m, f) therefore depends on KNTMP(m) alone:
+// not on nfld, the field's position, the number of tasks or the owner of m.
+// ==========================================================================================
+EMI_KERNEL_LB(256) void k_especnorm(const int *kntmp, const int *nesm0, const int *npme /* [nump], of the local wavenumbers */, int ntile,
+                                    const real_t *sp, int nfld, const real_t *pmet, double *out /* [nump][nfld] */) {
+  EMI_FP_STRICT();
+  EMI_LDS_DECL;
+  double *red = (double *)EMI_LDS_PTR;  // [3][64]
+  const int ml = EMI_BID / ntile, tile = EMI_BID - ml * ntile;
+  const int lane = EMI_TID & 63, w = EMI_TID >> 6;
+  const int f = tile * 64 + lane;
+  const int K = kntmp[ml] + 1;
+  const int n0 = (w * K) >> 2, n1 = ((w + 1) * K) >> 2;
+  double s = 0.0;
+  if (f < nfld) {
+    const real_t *p = sp + ((long long)nesm0[ml] + 4LL * n0) * nfld + f;
+    const real_t *wm = pmet ? pmet + npme[ml] + n0 : nullptr;
+    int n = n0;
+    for (; n + 4 <= n1; n += 4) {
+      real_t v[16];
+#pragma unroll
+      for (int k = 0; k < 16; k++) v[k] = p[(long long)k * nfld];
+      double wt[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) wt[j] = wm ? (double)wm[j] : 1.0;
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const double a = (double)v[4 * j], b = (double)v[4 * j + 1], c = (double)v[4 * j + 2], d = (double)v[4 * j + 3];
+        s += wt[j] * (((a * a + b * b) + c * c) + d * d);
+      }
+      p += 16LL * nfld;
+      if (wm) wm += 4;
+    }
+    for (; n < n1; n++) {
+      const double a = (double)p[0], b = (double)p[nfld], c = (double)p[2LL * nfld], d = (double)p[3LL * nfld];
+      s += (wm ? (double)wm[0] : 1.0) * (((a * a + b * b) + c * c) + d * d);
+      p += 4LL * nfld;
+      if (wm) wm += 1;
+    }
+  }
+  if (w > 0) red[(w - 1) * 64 + lane] = s;
+  EMI_SYNC();
+  if (w == 0 && f < nfld) out[(long long)ml * nfld + f] = ((s + red[lane]) + red[64 + lane]) + red[128 + lane];
+}
+
+// ==========================================================================================
 // k_vd2uv: VORDIV_TO_UV (cpu/external/vordiv_to_uv.F90 -> cpu/internal/vd2uv_mod.F90:79-120 = PRFI1B + VDTUV, vdtuv_mod.F90:97-143):
 //   U_n = i m L_n D_n + (n-1) e_n L_(n-1) vor_(n-1) - (n+2) e_(n+1) L_(n+1) vor_(n+1)
 //   V_n = i m L_n vor_n - (n-1) e_n L_(n-1) D_(n-1) + (n+2) e_(n+1) L_(n+1) D_(n+1),   L_n = RLAPIN(n) = -a^2 / (n (n+1)),

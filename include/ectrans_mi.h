@@ -241,7 +241,8 @@ int emi_dir_transad(int kresol, const emi_dirtrans_t *args);
  * numbering of emi_setup; emi_inq_int(kresol, "ldlam") tells them apart.  INTEGRATION.md ("Limited-area transforms") defines the
  * transform; in short, per x-wavenumber m and n = 0 .. KNTMP(m) the spectral arrays hold four reals (a_r, a_i, b_r, b_i) with the field
  * index fastest, PSPEC(nfld, nspec2), and grid arrays hold the rows one after the other.
- * A limited-area handle serves emi_einv_trans, emi_edir_trans, the inquiries, emi_wait and emi_release; every spherical routine
+ * A limited-area handle serves emi_einv_trans, emi_edir_trans, emi_especnorm, emi_egpnorm, emi_edist_spec / emi_egath_spec /
+ * emi_edist_grid / emi_egath_grid, the inquiries, emi_wait and emi_release; every spherical routine
  * returns EMI_ERR_UNSUPPORTED on it, and the two E-transforms return it on a handle of emi_setup.  NPRTRV > 1 is refused.
  * Further inquiries of such a handle -- emi_inq_int: "ldlam" "nmsmax" ("nsmax" is KSMAX) "ndgux"; emi_inq_int_array, all over
  * m = 0 .. KMSMAX unless stated: "kntmp" "ncpl2m" "ncpl4m" "npme" "nesm0" (1-based, -99 for the wavenumbers of other tasks)
@@ -263,6 +264,24 @@ int emi_esetup(const emi_esetup_t *cfg, int *kresol);
  * are there.                                                                                                                       */
 int emi_einv_trans(int kresol, const emi_invtrans_t *args, const void *meanu, const void *meanv);
 int emi_edir_trans(int kresol, const emi_dirtrans_t *args, void *meanu, void *meanv);
+
+/* ---- ESPECNORM (etrans/include/etrans/especnorm.h; espnorm_ctl_mod.F90, espnormd_mod.F90) -----------------------------------------
+ * PNORM(f) = sqrt( sum over m = 0 .. KMSMAX of S(f, m) ),  S(f, m) = sum over n = 0 .. KNTMP(m) of w(m, n) (a_r^2 + a_i^2 + b_r^2 + b_i^2)
+ * with the four reals of (m, n) at NESM0(m) + 4 n of PSPEC(f, :) -- all four of every (m, n), the entries the inverse transform ignores
+ * included.  pmet: NULL (w = 1), or npmet reals of the handle's precision in HOST memory, read zero-based: w(m, n) = pmet[NPME(m) + n],
+ * NPME(0) = 1, so element 0 is never read and NPME(KMSMAX) + KNTMP(KMSMAX) + 1 = NSPEC2G / 4 + 1 elements are needed.  spec: host or
+ * device memory; the call runs on the null stream behind the last transform of the resolution.  Sums are in double in both precisions,
+ * and the summation order of one (m, f) depends on KNTMP(m) alone: the norms are the same bytes for any number of fields in the call,
+ * any position of the field and any number of tasks.
+ * emi_especnorm_partial: sums (host) = double[nump][nfld], S(f, m) of this task's wavenumbers in MYMS order.
+ * emi_especnorm: norms (host, nfld) on every task; several tasks gather the sums through the host collectives.                    */
+int emi_especnorm_partial(int kresol, int mem_space, const void *spec, int nfld, const void *pmet, int npmet, double *sums);
+int emi_especnorm(int kresol, int mem_space, const void *spec, int nfld, const void *pmet, int npmet, double *norms);
+/* ---- EGPNORM_TRANS (etrans/include/etrans/egpnorm_trans.h): emi_gpnorm on a limited-area handle.  PAVE(f) = sum over ALL NDGL rows,
+ * extension zone included, of (1 / NDGL) (sum of the row's points, in double) / NDLON -- 1 / NDGL rounded to the handle's precision
+ * first, as the reference does; PMIN / PMAX over all points.  The reference's EGPNORM_OLD variant is not provided.               */
+int emi_egpnorm(int kresol, int mem_space, const void *gp, int gp_nfld, int kfields, int kproma, double *ave, double *pmin, double *pmax,
+                int ave_only);
 
 /* ---- SPECNORM (trans/include/ectrans/specnorm.h:12) --------------------------------- */
 int emi_specnorm(int kresol, int mem_space, const void *spec, int nfld, double *norms /* host */);
@@ -305,6 +324,14 @@ int emi_dist_spec(int kresol, const void *specg, int nfld, const int *kfrom, con
 int emi_gath_spec(int kresol, void *specg, int nfld, const int *kto, const void *spec);
 int emi_dist_grid(int kresol, const void *gpg, int nfld, const int *kfrom, const int *ksort, int kproma, void *gp);
 int emi_gath_grid(int kresol, void *gpg, int nfld, const int *kto, int kproma, const void *gp);
+/* EDIST_SPEC / EGATH_SPEC / EDIST_GRID / EGATH_GRID (etrans/include/etrans/edist_spec.h ...): the same four on a limited-area handle,
+ * with the same semantics (host arrays, kfrom / kto / ksort, NPRTRV = 1).  A global spectral field is the one-task layout: m = 0 ..
+ * KMSMAX ascending, 4 (KNTMP(m) + 1) reals each, NSPEC2G in all; a global grid field the NDGL x NDLON points row after row.  The
+ * spherical four refuse a limited-area handle and these refuse a Gaussian one.                                                  */
+int emi_edist_spec(int kresol, const void *specg, int nfld, const int *kfrom, const int *ksort, void *spec);
+int emi_egath_spec(int kresol, void *specg, int nfld, const int *kto, const void *spec);
+int emi_edist_grid(int kresol, const void *gpg, int nfld, const int *kfrom, const int *ksort, int kproma, void *gp);
+int emi_egath_grid(int kresol, void *gpg, int nfld, const int *kto, int kproma, const void *gp);
 /* What emi_init was given (EMI_ERR_STATE before it): a Fortran host whose transport attached first (emi_mpi_attach,
  * emi_rccl_attach) learns its task number from here in SETUP_TRANS0.                                                 */
 int emi_inq_tasks(int *nproc, int *myproc);
