@@ -20,7 +20,8 @@ import os
 import numpy as np
 
 __all__ = ["TransError", "setup_trans0", "setup_trans", "inv_trans", "dir_trans", "trans_inq", "specnorm",
-           "trans_release", "trans_end", "lib", "build", "esetup_trans", "einv_trans", "edir_trans", "etrans_inq"]
+           "trans_release", "trans_end", "lib", "build", "esetup_trans", "einv_trans", "edir_trans", "etrans_inq",
+           "einv_transad", "edir_transad"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBPATH = os.path.join(_HERE, "libectrans_mi.so")
@@ -158,6 +159,8 @@ def _bind(L):
         L.emi_esetup.argtypes = [C.POINTER(_ESetup), ip]
         L.emi_einv_trans.argtypes = [C.c_int, C.POINTER(_Inv), C.c_void_p, C.c_void_p]
         L.emi_edir_trans.argtypes = [C.c_int, C.POINTER(_Dir), C.c_void_p, C.c_void_p]
+        L.emi_einv_transad.argtypes = [C.c_int, C.POINTER(_Inv), C.c_void_p, C.c_void_p]
+        L.emi_edir_transad.argtypes = [C.c_int, C.POINTER(_Dir), C.c_void_p, C.c_void_p]
     if hasattr(L, "emi_especnorm"):  # (an older build loaded for an A/B run)
         L.emi_especnorm.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, dp]
         L.emi_especnorm_partial.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, dp]
@@ -619,6 +622,54 @@ def edir_trans(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, p
     a.mem_space = _space(mem_space, space)
     a.stream = stream
     _chk(lib().emi_edir_trans(kresol, C.byref(a), mu, mv))
+
+
+def einv_transad(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, pspsc3b=None, pspsc2=None, fspgl_proc=None,
+                 ldscders=False, ldvorgp=False, lddivgp=False, lduvder=False, kproma=None, pgp=None, pgpuv=None, pgp3a=None,
+                 pgp3b=None, pgp2=None, pmeanu=None, pmeanv=None, stream=None, kvsetuv=None, kvsetsc=None, kvsetsc2=None,
+                 kvsetsc3a=None, kvsetsc3b=None, mem_space=None):
+    """EINV_TRANSAD (einv_transad.h): the transpose of ``einv_trans`` -- reads pgp*, writes psp*, pmeanu and pmeanv (overwritten;
+    the reference adds to them).  Inner products: plain sums over the grid points and over the NSPEC2 reals and the means, no weights.
+    With ldscders / ldvorgp / lddivgp / lduvder the grid arrays carry the derivative / vorticity / divergence inputs in
+    EINV_TRANS's layout.  Entries that do not enter EINV_TRANS come back as zeros."""
+    if fspgl_proc is not None:
+        raise TransError("EINV_TRANSAD: FSPGL_PROC is not supported")
+    if any(k is not None for k in (kvsetuv, kvsetsc, kvsetsc2, kvsetsc3a, kvsetsc3b)) and _DIST.get("nprtrv", 1) > 1:
+        raise TransError("EINV_TRANSAD: KVSET arguments: V-sets are not available on a limited-area handle")
+    a, space, keep = _Inv(), [None, real_dtype(kresol)], []
+    nspec2, ngptot = trans_inq(kresol, "nspec2"), trans_inq(kresol, "ngptot")
+    nproma = int(kproma) if kproma else ngptot
+    _fill_spec(a, space, keep, pspvor, pspdiv, pspscalar, pspsc3a, pspsc3b, pspsc2, nspec2)
+    _fill_grid(a, space, keep, pgp, pgpuv, pgp3a, pgp3b, pgp2, nproma, (ngptot - 1) // nproma + 1,
+               (pspvor, pspdiv, pspscalar, pspsc3a, pspsc3b, pspsc2))
+    a.ldscders, a.ldvorgp, a.lddivgp, a.lduvder = int(ldscders), int(ldvorgp), int(lddivgp), int(lduvder)
+    a.kproma = nproma
+    mu, mv = _mean_ptr(pmeanu, a.nf_uv, space, keep, "PMEANU"), _mean_ptr(pmeanv, a.nf_uv, space, keep, "PMEANV")
+    a.mem_space = _space(mem_space, space)
+    a.stream = stream
+    _chk(lib().emi_einv_transad(kresol, C.byref(a), mu, mv))
+
+
+def edir_transad(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None, pspsc3b=None, pspsc2=None, kproma=None,
+                 pgp=None, pgpuv=None, pgp3a=None, pgp3b=None, pgp2=None, pmeanu=None, pmeanv=None, aux_proc=None, stream=None,
+                 kvsetuv=None, kvsetsc=None, kvsetsc2=None, kvsetsc3a=None, kvsetsc3b=None, mem_space=None):
+    """EDIR_TRANSAD (edir_transad.h): the transpose of ``edir_trans`` -- reads psp*, pmeanu and pmeanv, writes pgp* (overwritten).
+    The entries that EDIR_TRANS writes as structural zeros are not read."""
+    if aux_proc is not None:
+        raise TransError("EDIR_TRANSAD: AUX_PROC is not supported")
+    if any(k is not None for k in (kvsetuv, kvsetsc, kvsetsc2, kvsetsc3a, kvsetsc3b)) and _DIST.get("nprtrv", 1) > 1:
+        raise TransError("EDIR_TRANSAD: KVSET arguments: V-sets are not available on a limited-area handle")
+    a, space, keep = _Dir(), [None, real_dtype(kresol)], []
+    nspec2, ngptot = trans_inq(kresol, "nspec2"), trans_inq(kresol, "ngptot")
+    nproma = int(kproma) if kproma else ngptot
+    _fill_spec(a, space, keep, pspvor, pspdiv, pspscalar, pspsc3a, pspsc3b, pspsc2, nspec2)
+    _fill_grid(a, space, keep, pgp, pgpuv, pgp3a, pgp3b, pgp2, nproma, (ngptot - 1) // nproma + 1,
+               (pspvor, pspdiv, pspscalar, pspsc3a, pspsc3b, pspsc2))
+    a.kproma = nproma
+    mu, mv = _mean_ptr(pmeanu, a.nf_uv, space, keep, "PMEANU"), _mean_ptr(pmeanv, a.nf_uv, space, keep, "PMEANV")
+    a.mem_space = _space(mem_space, space)
+    a.stream = stream
+    _chk(lib().emi_edir_transad(kresol, C.byref(a), mu, mv))
 
 
 _E_INT_SCALARS = ("nspec", "nspec2", "nspec2g", "nspec2mx", "nump", "ngptot", "ngptotg", "ngptotmx", "nprtrw", "mysetw", "mysetv",

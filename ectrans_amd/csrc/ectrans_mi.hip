@@ -2536,6 +2536,10 @@ static int set_lds_attrs() {
   EMI_CHECK(hipFuncSetAttribute((const void *)emi_f64::k_lam_dir, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   EMI_CHECK(hipFuncSetAttribute((const void *)emi_f32::k_lam_inv, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   EMI_CHECK(hipFuncSetAttribute((const void *)emi_f32::k_lam_dir, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  EMI_CHECK(hipFuncSetAttribute((const void *)emi_f64::k_lam_inv_ad, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  EMI_CHECK(hipFuncSetAttribute((const void *)emi_f64::k_lam_dir_ad, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  EMI_CHECK(hipFuncSetAttribute((const void *)emi_f32::k_lam_inv_ad, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  EMI_CHECK(hipFuncSetAttribute((const void *)emi_f32::k_lam_dir_ad, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   EMI_CHECK(hipFuncSetAttribute((const void *)emi_f64::k_fft_inv, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   EMI_CHECK(hipFuncSetAttribute((const void *)emi_f64::k_fft_dir, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   EMI_CHECK(hipFuncSetAttribute((const void *)emi_f32::k_fft_inv, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -2806,6 +2810,8 @@ struct Batch {
   int ldw = 0, ntiles = 0;                 // row width (2 x 64 x its column tiles); the column tiles that hold fields
   size_t off_g = 0, off_s = 0, off_f = 0;  // offsets of its GridFld, of its SpecSrc (inverse) or SpecDst (direct), of its FuseDst
   int ng = 0, ns = 0;                      // numbers of GridFld and of SpecSrc / SpecDst
+  size_t off_l = 0, off_c = 0;             // EINV_TRANSAD: offsets of its LamSlot and of its chunk starts (nchunk + 1 of them)
+  int nchunk = 0;
   LegMaps *maps = nullptr;
 };
 // appends n descriptors to the upload of a call, 256-byte aligned, and returns their offset
@@ -2960,8 +2966,12 @@ static int inv_pipeline(Plan &P, const Call &d, const Fields &f, std::vector<Gri
       // the y-direction FFT is timed in the Legendre slot
       const int nchunk = (bt.ns + P.lamdev.fbk - 1) / P.lamdev.fbk;
       const int ivl = g_pt.start(1, s);
-      EMI_LAUNCH_P(P.esz, k_lam_inv, (long long)P.nump * nchunk, P.lam_nthr, P.lam_lds, s, P.g, P.lamdev, P.ftab, d_bl, bt.ns, (const RT *)d.meanu, (const RT *)d.meanv,
-                   (RT *)FBl, ldw, nchunk);
+      if (adj)
+        EMI_LAUNCH_P(P.esz, k_lam_inv_ad, (long long)P.nump * nchunk, P.lam_nthr, P.lam_lds, s, P.g, P.lamdev, P.ftab, d_bl, bt.ns, (const RT *)d.meanu, (const RT *)d.meanv,
+                     (RT *)FBl, ldw, nchunk);
+      else
+        EMI_LAUNCH_P(P.esz, k_lam_inv, (long long)P.nump * nchunk, P.lam_nthr, P.lam_lds, s, P.g, P.lamdev, P.ftab, d_bl, bt.ns, (const RT *)d.meanu, (const RT *)d.meanv,
+                     (RT *)FBl, ldw, nchunk);
       g_pt.stop(ivl, s);
       return 0;
     }
@@ -3043,6 +3053,25 @@ static int dir_pipeline(Plan &P, const Call &d, const Fields &f, const std::vect
   for (auto &b : batches) maxb = std::max(maxb, (int)b.size());
   const int bfpad = roundup(maxb, 64);  // every batch has its own row width (2 x its fields rounded up to 64)
   const bool fuse_dir = !(test_paths() & 4) && !P.lam;  // plain-copy fields leave k_leg_dir's epilogue straight for the caller's arrays
+  // EINV_TRANSAD: k_lam_dir_ad holds whole atoms in its work array -- {u, v [, vor] [, div]} and {scalar [, N-S input]}, the E-W inputs
+  // folded into their base fields.  An atom larger than the fields per workgroup of the handle takes a larger work array where the
+  // LDS holds one.
+  const bool lam_ad = P.lam && adj;
+  int lam_cap = P.lamdev.fbk;
+  size_t lam_lds = P.lam_lds;
+  if (lam_ad) {
+    const size_t per_field = P.lam_lds / P.lamdev.fbk;
+    const int need = std::max(nuv ? 2 + (f.vorgp ? 1 : 0) + (f.divgp ? 1 : 0) : 0, nsc ? 1 + (f.scders ? 1 : 0) : 0);
+    if (need > lam_cap) {
+      if (need * per_field > 160 * 1024)
+        EMI_FAIL(EMI_ERR_UNSUPPORTED,
+                 "EINV_TRANSAD: LDVORGP / LDDIVGP WITH KDGL = %d: A WIND FIELD NEEDS %d FIELDS OF %zu BYTES IN ONE WORK ARRAY, THE LDS HOLDS 160 KIB (LDVORGP NEEDS 4 "
+                 "FIELDS, LDDIVGP ALONE 3, NEITHER 2)",
+                 P.ndgl, need, per_field);
+      lam_cap = need, lam_lds = need * per_field;
+    }
+  }
+  const int lam_nthr = std::min(512, fft_threads(lam_lds));
   std::vector<Batch> bats;
   std::vector<char> hdesc;
   for (auto &b : batches) {
@@ -3055,6 +3084,31 @@ static int dir_pipeline(Plan &P, const Call &d, const Fields &f, const std::vect
       bg.push_back(gin[b[i]]);
     }
     auto at_ = [&](int x) { return x >= 0 ? loc[x] : -1; };  // field number -> position in this batch's W
+    std::vector<LamSlot> bsl;
+    std::vector<int> bcs;
+    if (lam_ad) {  // the slots of the batch, atom by atom, and the chunks of whole atoms; loc: field number -> slot from here on
+      std::map<int, int> sloc;
+      auto slot = [&](int fn, int few) {
+        if (fn < 0) return;
+        sloc[fn] = (int)bsl.size();
+        bsl.push_back(LamSlot{loc[fn], at_(few)});
+      };
+      bcs.push_back(0);
+      for (size_t i = 0; i < b.size(); i++) {
+        const int fn = b[i], n0 = (int)bsl.size();
+        if (fn < nuv) {
+          slot(fn, num[GF_UEW][fn]), slot(nuv + fn, num[GF_VEW][fn]), slot(num[GF_VOR][fn], -1), slot(num[GF_DIV][fn], -1);
+        } else if (fn >= 2 * nuv && fn < 2 * nuv + nsc) {
+          slot(fn, num[GF_SCEW][fn - 2 * nuv]), slot(num[GF_NSD][fn - 2 * nuv], -1);
+        }
+        if ((int)bsl.size() - bcs.back() > lam_cap) bcs.push_back(n0);
+      }
+      bcs.push_back((int)bsl.size());
+      for (size_t i = 0; i < b.size(); i++) {  // (the E-W inputs have no slot: they are not sources any more)
+        auto it = sloc.find(b[i]);
+        loc[b[i]] = it == sloc.end() ? -1 : it->second;
+      }
+    }
     for (size_t i = 0; i < b.size(); i++) {
       int fn = b[i];
       if (fn < nuv) {  // u_i -> vor_i and div_i outputs
@@ -3068,7 +3122,7 @@ static int dir_pipeline(Plan &P, const Call &d, const Fields &f, const std::vect
         const int isc = fn - 2 * nuv;
         const ScalarRef &r = f.sc[isc];
         SpecDst sd{};
-        sd.kind = SPO_COPY; sd.src0 = (int)i; sd.src1 = sd.src2 = sd.src3 = sd.src4 = -1;
+        sd.kind = SPO_COPY; sd.src0 = loc[fn]; sd.src1 = sd.src2 = sd.src3 = sd.src4 = -1;
         switch (r.arr) {
           case 0: sd.dst = d.spscalar; sd.stride = d.nf_scalar; sd.idx = r.lev; break;
           case 1: sd.dst = d.spsc2; sd.stride = d.nf_sc2; sd.idx = r.lev; break;
@@ -3091,6 +3145,11 @@ static int dir_pipeline(Plan &P, const Call &d, const Fields &f, const std::vect
     bt.ng = (int)bg.size(), bt.off_g = append_desc(hdesc, bg.data(), bg.size());
     bt.ns = (int)bo.size(), bt.off_s = append_desc(hdesc, bo.data(), bo.size());
     bt.off_f = append_desc(hdesc, bf.data(), bf.size());
+    if (lam_ad) {
+      bt.off_l = append_desc(hdesc, bsl.data(), bsl.size());
+      bt.off_c = append_desc(hdesc, bcs.data(), bcs.size());
+      bt.nchunk = (int)bcs.size() - 1;
+    }
     bats.push_back(bt);
   }
   // stream B: FFTs
@@ -3111,8 +3170,12 @@ static int dir_pipeline(Plan &P, const Call &d, const Fields &f, const std::vect
       // in the order of their source fields, bt.ng fields in the buffer); timed in the Legendre slot
       const int nchunk = (bt.ng + P.lamdev.fbk - 1) / P.lamdev.fbk;
       const int ivl = g_pt.start(1, s);
-      EMI_LAUNCH_P(P.esz, k_lam_dir, (long long)P.nump * nchunk, P.lam_nthr, P.lam_lds, s, P.g, P.lamdev, P.ftab, (const SpecDst *)((char *)P.d_desc + bt.off_s), bt.ns, bt.ng,
-                   (RT *)d.meanu, (RT *)d.meanv, (const RT *)FBl, ldw, nchunk);
+      if (lam_ad)
+        EMI_LAUNCH_P(P.esz, k_lam_dir_ad, (long long)P.nump * bt.nchunk, lam_nthr, lam_lds, s, P.g, P.lamdev, P.ftab, (const SpecDst *)((char *)P.d_desc + bt.off_s), bt.ns,
+                     (const LamSlot *)((char *)P.d_desc + bt.off_l), (const int *)((char *)P.d_desc + bt.off_c), (RT *)d.meanu, (RT *)d.meanv, (const RT *)FBl, ldw, bt.nchunk);
+      else
+        EMI_LAUNCH_P(P.esz, k_lam_dir, (long long)P.nump * nchunk, P.lam_nthr, P.lam_lds, s, P.g, P.lamdev, P.ftab, (const SpecDst *)((char *)P.d_desc + bt.off_s), bt.ns, bt.ng,
+                     (RT *)d.meanu, (RT *)d.meanv, (const RT *)FBl, ldw, nchunk);
       g_pt.stop(ivl, s);
       done();
       return 0;
@@ -4103,11 +4166,11 @@ static int resolve_call(const char *who, const A *ap, A &a) {
 }
 // INV_TRANS / DIR_TRANSAD run the inverse pipeline, DIR_TRANS / INV_TRANSAD the direct one
 static int transform(int kresol, const Call &c, bool inverse, bool adj, bool lam = false) {
-  const char *who = lam ? (inverse ? "EINV_TRANS" : "EDIR_TRANS") : inverse ? (adj ? "DIR_TRANSAD" : "INV_TRANS") : (adj ? "INV_TRANSAD" : "DIR_TRANS");
+  const char *who = lam ? (inverse ? (adj ? "EDIR_TRANSAD" : "EINV_TRANS") : (adj ? "EINV_TRANSAD" : "EDIR_TRANS")) : inverse ? (adj ? "DIR_TRANSAD" : "INV_TRANS") : (adj ? "INV_TRANSAD" : "DIR_TRANS");
   Plan *Pp = get_plan(kresol);
   if (!Pp) EMI_FAIL(EMI_ERR_STATE, "%s: unknown resolution %d", who, kresol);
   if (Pp->lam && !lam)
-    EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): it serves EINV_TRANS and EDIR_TRANS", who, kresol);
+    EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): it serves EINV_TRANS, EDIR_TRANS and their adjoints", who, kresol);
   if (!Pp->lam && lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is not a limited-area handle: it was not set up by ESETUP_TRANS", who, kresol);
   if (lam && c.vsets) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: KVSET arguments: V-sets are not available on a limited-area handle", who);
   // A handle set up with LDLL holds the inverse panels of its lat-lon rows and nothing else: no Gaussian grid beside them (the
@@ -4149,6 +4212,23 @@ extern "C" int emi_edir_trans(int kresol, const emi_dirtrans_t *args, void *mean
   Call c = to_call(a);
   c.meanu = meanu, c.meanv = meanv;
   return transform(kresol, c, false, false, true);
+}
+// EINV_TRANSAD / EDIR_TRANSAD (etrans/include/etrans/einv_transad.h, edir_transad.h): the argument blocks of the forward routines with the
+// intents swapped, for plain Euclidean inner products on both sides (the means among the spectral entries).  Outputs are overwritten.
+extern "C" int emi_einv_transad(int kresol, const emi_invtrans_t *args, void *meanu, void *meanv) {
+  emi_invtrans_t a;
+  if (resolve_call("EINV_TRANSAD", args, a)) return EMI_ERR_ARG;
+  if (a.ldlatlon) EMI_FAIL(EMI_ERR_UNSUPPORTED, "EINV_TRANSAD: LDLATLON is not available on a limited-area handle");
+  Call c = to_call(a);
+  c.meanu = meanu, c.meanv = meanv;
+  return transform(kresol, c, false, true, true);
+}
+extern "C" int emi_edir_transad(int kresol, const emi_dirtrans_t *args, const void *meanu, const void *meanv) {
+  emi_dirtrans_t a;
+  if (resolve_call("EDIR_TRANSAD", args, a)) return EMI_ERR_ARG;
+  Call c = to_call(a);
+  c.meanu = (void *)meanu, c.meanv = (void *)meanv;
+  return transform(kresol, c, true, true, true);
 }
 extern "C" int emi_wait(int kresol) {
   if (!G.init) EMI_FAIL(EMI_ERR_STATE, "emi_wait: SETUP_TRANS0 has not been called");

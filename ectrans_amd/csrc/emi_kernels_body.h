@@ -3479,5 +3479,189 @@ EMI_KERNEL_LAM(EMI_LAM_WAVES) void k_lam_dir(EmiGeomDev g, LamDev lam, FftTabDev
   }
 }
 
+// ---- The adjoints EDIR_TRANSAD / EINV_TRANSAD: kernels of their own, so that the forward ones above keep their code and registers.
+// Inner products: plain sums over the grid points and over the NSPEC2 reals (+ the means), no SPECNORM-type weights.  With
+// w_0 = 1, w_k = 2 (k > 0): the transpose of the c2r in x is w_m x the unnormalised r2c, that of the r2c is the c2r of F / w_m, and the
+// same holds in y for the pair (C(n), C(NDGL - n)) <-> (a, b).  The x-direction kernels run their adjoint branches (no weights).
+//
+// k_lam_inv_ad (EDIR_TRANSAD): k_lam_inv with the loader of the transpose of k_lam_dir's epilogue -- coefficients times 1 / (w_m w_n);
+// u = d/dy vor - d/dx div, v = -d/dx vor - d/dy div (the transpose of EUVTVD), their (0, 0) real parts from the means.  The entries
+// that EDIR_TRANS writes as structural zeros (imaginary parts of n = 0, b of m = 0) are not read.
+EMI_DEVFN void lam_get_ad(const void *av, int sa, int ia, long long isp, int m, int n, real2 &a, real2 &b) {
+  const real_t *p = (const real_t *)av + isp * sa + ia;
+  const real_t z = (real_t)0.0;
+  a = mk2(p[0], n == 0 ? z : p[sa]);
+  b = m == 0 ? mk2(z, z) : mk2(p[2 * (long long)sa], n == 0 ? z : p[3 * (long long)sa]);
+}
+EMI_KERNEL_LAM(EMI_LAM_WAVES) void k_lam_inv_ad(EmiGeomDev g, LamDev lam, FftTabDev T, const SpecSrc *flds, int nfld, const real_t *meanu,
+                                 const real_t *meanv, real_t *FB, int ldf, int nchunk) {
+  EMI_LDS_DECL;
+  real2 *a = (real2 *)EMI_LDS_PTR;
+  const int ml = EMI_BID / nchunk, f0 = (EMI_BID - ml * nchunk) * lam.fbk;
+  const int nfl = (nfld - f0) < lam.fbk ? (nfld - f0) : lam.fbk;
+  const FftPlanDev &pl = T.plans[lam.yplan];
+  const int L = lam.ndgl, S = pl.S, fs = lam.fs, blue = pl.blue;
+  const int m = g.mval[ml], nm = lam.kntmp[ml];
+  const unsigned short *perm = T.perm + pl.perm_off;
+  const real2 *chirp = (const real2 *)T.chirp + pl.chirp_off;
+  const real_t kx = (real_t)(lam.exwn * (double)m);
+  const real_t rwm = m == 0 ? (real_t)1.0 : (real_t)0.5;
+  for (int idx = EMI_TID; idx < (nm + 1) * nfl; idx += EMI_NTHREADS) {
+    const int n = idx / nfl, fl = idx - n * nfl;
+    const SpecSrc s = flds[f0 + fl];
+    const long long isp = lam.nesm0[ml] + 4LL * n;
+    const real_t ky = (real_t)(lam.eywn * (double)n);
+    real2 ca, cb;
+    if (s.kind == SPK_COPY) {
+      lam_get_ad(s.a, s.sa, s.ia, isp, m, n, ca, cb);
+    } else if (m == 0 && n == 0) {  // SPK_U_AD, SPK_V_AD: s.a = vorticity, s.b = divergence; their (0, 0) entries do not enter
+      const real_t *mean = s.kind == SPK_U_AD ? meanu : meanv;
+      ca = mk2(mean ? mean[s.ia] : (real_t)0.0, (real_t)0.0), cb = mk2((real_t)0.0, (real_t)0.0);
+    } else {
+      real2 va, vb, da, db;
+      lam_get_ad(s.a, s.sa, s.ia, isp, m, n, va, vb);
+      lam_get_ad(s.b, s.sb, s.ib, isp, m, n, da, db);
+      if (s.kind == SPK_U_AD) {
+        ca = mk2(kx * db.x - ky * va.y, kx * db.y + ky * va.x);
+        cb = mk2(-kx * da.x - ky * vb.y, -kx * da.y + ky * vb.x);
+      } else {
+        ca = mk2(kx * vb.x + ky * da.y, kx * vb.y - ky * da.x);
+        cb = mk2(-kx * va.x + ky * db.y, -kx * va.y - ky * db.x);
+      }
+    }
+    const real_t w = n == 0 ? rwm : (real_t)0.5 * rwm;  // 1 / (w_m w_n)
+    ca = cscale(ca, w), cb = cscale(cb, w);
+    real2 *af = a + (long long)fl * fs;
+    const real2 cp = mk2(ca.x - cb.y, ca.y + cb.x);  // a + i b
+    af[FPAD(blue ? n : (int)perm[n])] = blue ? cmulc(cp, chirp[n]) : cp;
+    if (n > 0) {
+      const int k = L - n;
+      const real2 cm = mk2(ca.x + cb.y, cb.x - ca.y);  // conj(a) + i conj(b)
+      af[FPAD(blue ? k : (int)perm[k])] = blue ? cmulc(cm, chirp[k]) : cm;
+    }
+  }
+  const int nz = L - 2 * nm - 1;
+  for (int idx = EMI_TID; idx < nz * nfl; idx += EMI_NTHREADS) {
+    const int kk = idx / nfl, fl = idx - kk * nfl, k = nm + 1 + kk;
+    a[(long long)fl * fs + FPAD(blue ? k : (int)perm[k])] = mk2((real_t)0.0, (real_t)0.0);
+  }
+  EMI_SYNC();
+  if (blue)
+    blue_conv(a, nfl, fs, pl, T, 1, L, 0);
+  else
+    run_dit(a, nfl, fs, S, pl, T, 0, pl.nfac, 1, +1);
+  const real_t invL = blue ? (real_t)(1.0 / (double)S) : (real_t)1.0;
+  for (int idx = EMI_TID; idx < L * nfl; idx += EMI_NTHREADS) {
+    const int j = idx / nfl, fl = idx - j * nfl;
+    real2 z = a[(long long)fl * fs + FPAD(j)];
+    if (blue) z = cscale(cmulc(z, chirp[j]), invL);
+    if (m == 0) z.y = (real_t)0.0;
+    *(real2 *)(FB + (unsigned long long)(unsigned)(lam.rowbase[j] + ml) * (unsigned)ldf + 2 * (f0 + fl)) = z;
+  }
+}
+
+// k_lam_dir_ad (EINV_TRANSAD): k_lam_dir with the epilogue of the transpose of k_lam_inv's loader -- coefficients times w_m w_n;
+//   vor = lap^-1 (d/dy u - d/dx v) [+ the grid vorticity input],  div = lap^-1 (-d/dx u - d/dy v) [+ the grid divergence input],
+//   scalar = value - d/dy (its N-S derivative input);  the (0, 0) coefficients of u, v to the means, those of the wind part zero.
+// The work array holds SLOTS, not buffer fields: the E-W derivative input of a field arrives from the x-direction kernels times EXWN
+// and is added to that field's slot times -i m by the loader (-d/dx is constant per workgroup and commutes with the y-transform).
+// A workgroup holds the slots [cstart[c], cstart[c + 1]) of its chunk c: whole atoms {u, v [, vor] [, div]} / {scalar [, N-S input]},
+// cut on the host, at most (LDS bytes of the launch) / (bytes per field) of them.  outs: ascending in src0, src* are slot numbers.
+EMI_KERNEL_LAM(EMI_LAM_WAVES) void k_lam_dir_ad(EmiGeomDev g, LamDev lam, FftTabDev T, const SpecDst *outs, int nout, const LamSlot *slots, const int *cstart,
+                                 real_t *meanu, real_t *meanv, const real_t *FB, int ldf, int nchunk) {
+  EMI_LDS_DECL;
+  real2 *a = (real2 *)EMI_LDS_PTR;
+  const int ml = EMI_BID / nchunk, ic = EMI_BID - ml * nchunk;
+  const int f0 = cstart[ic], nfl = cstart[ic + 1] - f0;
+  const FftPlanDev &pl = T.plans[lam.yplan];
+  const int L = lam.ndgl, S = pl.S, fs = lam.fs, blue = pl.blue;
+  const int m = g.mval[ml], nm = lam.kntmp[ml];
+  const unsigned short *perm = T.perm + pl.perm_off;
+  const real2 *chirp = (const real2 *)T.chirp + pl.chirp_off;
+  const real_t zm = (real_t)m;
+  for (int idx = EMI_TID; idx < L * nfl; idx += EMI_NTHREADS) {
+    const int j = idx / nfl, fl = idx - j * nfl;
+    const LamSlot sl = slots[f0 + fl];
+    const real_t *row = FB + (unsigned long long)(unsigned)(lam.rowbase[j] + ml) * (unsigned)ldf;
+    real2 z = *(const real2 *)(row + 2 * sl.f);
+    if (sl.few >= 0) {
+      const real2 e = *(const real2 *)(row + 2 * sl.few);
+      z = mk2(z.x + zm * e.y, z.y - zm * e.x);
+    }
+    a[(long long)fl * fs + FPAD(blue ? j : (int)perm[j])] = blue ? cmul(z, chirp[j]) : z;
+  }
+  EMI_SYNC();
+  if (blue)
+    blue_conv(a, nfl, fs, pl, T, 0, L, 0);
+  else
+    run_dit(a, nfl, fs, S, pl, T, 0, pl.nfac, 1, -1);
+  int o0 = 0, o1 = 0;
+  {
+    int lo = 0, hi = nout;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (outs[mid].src0 < f0) lo = mid + 1; else hi = mid;
+    }
+    o0 = lo, hi = nout;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (outs[mid].src0 < f0 + nfl) lo = mid + 1; else hi = mid;
+    }
+    o1 = lo;
+  }
+  const int no = o1 - o0;
+  const real_t invL = blue ? (real_t)(1.0 / (double)S) : (real_t)1.0;
+  const real_t kx = (real_t)(lam.exwn * (double)m);
+  const real_t wm = m == 0 ? (real_t)1.0 : (real_t)2.0;
+  for (int idx = EMI_TID; idx < (nm + 1) * no; idx += EMI_NTHREADS) {
+    const int n = idx / no, oo = idx - n * no;
+    const SpecDst d = outs[o0 + oo];
+    const real_t ky = (real_t)(lam.eywn * (double)n);
+    const real_t w = n == 0 ? wm : (real_t)2.0 * wm;  // w_m w_n (lam_ab halves)
+    real2 ca, cb;
+    lam_ab(a + (long long)(d.src0 - f0) * fs, n, L, blue, chirp, invL, ca, cb);
+    ca = cscale(ca, w), cb = cscale(cb, w);
+    if (d.kind == SPO_SC_AD) {
+      if (d.src1 >= 0) {
+        real2 xa, xb;
+        lam_ab(a + (long long)(d.src1 - f0) * fs, n, L, blue, chirp, invL, xa, xb);
+        const real_t wk = w * ky;
+        ca = mk2(ca.x + wk * xa.y, ca.y - wk * xa.x), cb = mk2(cb.x + wk * xb.y, cb.y - wk * xb.x);
+      }
+    } else if (d.kind != SPO_COPY) {  // SPO_VOR_AD, SPO_DIV_AD: src0 = u, src1 = v, src4 = the grid vorticity / divergence input
+      real2 wa, wb;
+      lam_ab(a + (long long)(d.src1 - f0) * fs, n, L, blue, chirp, invL, wa, wb);
+      wa = cscale(wa, w), wb = cscale(wb, w);
+      if (m == 0 && n == 0) {
+        if (d.kind == SPO_VOR_AD) {
+          if (meanu) meanu[d.idx] = ca.x;
+          if (meanv) meanv[d.idx] = wa.x;
+        }
+        ca = cb = mk2((real_t)0.0, (real_t)0.0);
+      } else {
+        const real_t il = (real_t)1.0 / (kx * kx + ky * ky);  // -lap^-1
+        const real2 ua = ca, ub = cb;
+        if (d.kind == SPO_VOR_AD) {
+          ca = mk2(il * (-kx * wb.x + ky * ua.y), il * (-kx * wb.y - ky * ua.x));
+          cb = mk2(il * (kx * wa.x + ky * ub.y), il * (kx * wa.y - ky * ub.x));
+        } else {
+          ca = mk2(il * (-kx * ub.x - ky * wa.y), il * (-kx * ub.y + ky * wa.x));
+          cb = mk2(il * (kx * ua.x - ky * wb.y), il * (kx * ua.y + ky * wb.x));
+        }
+      }
+      if (d.src4 >= 0) {
+        real2 xa, xb;
+        lam_ab(a + (long long)(d.src4 - f0) * fs, n, L, blue, chirp, invL, xa, xb);
+        ca = mk2(ca.x + w * xa.x, ca.y + w * xa.y), cb = mk2(cb.x + w * xb.x, cb.y + w * xb.y);
+      }
+    }
+    // the entries that do not enter EINV_TRANS come out as zeros
+    if (n == 0) ca.y = (real_t)0.0, cb.y = (real_t)0.0;
+    if (m == 0) cb = mk2((real_t)0.0, (real_t)0.0);
+    real_t *p = (real_t *)d.dst + (lam.nesm0[ml] + 4LL * n) * d.stride + d.idx;
+    p[0] = ca.x, p[d.stride] = ca.y, p[2 * (long long)d.stride] = cb.x, p[3 * (long long)d.stride] = cb.y;
+  }
+}
+
 #undef FROW
 #undef emi_mfma_f64_16x16x4

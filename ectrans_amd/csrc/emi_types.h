@@ -89,6 +89,9 @@ struct LamDev {
   const int *nesm0;    // [nump] 0-based start of its block of 4 (KNTMP + 1) reals in the caller's spectral dimension
   const int *rowbase;  // [ndgl] row of (row j, local wavenumber 0) in the y-side Fourier buffer: (j, ml) is row rowbase[j] + ml
 };
+struct LamSlot {  // k_lam_dir_ad: one field of a workgroup's work array
+  int f, few;     // its field in the Fourier buffer; the E-W derivative input folded into it (-1: none)
+};
 enum { GM_PLAIN = 0, GM_ACOS = 1, GM_EWDER = 2, GM_EWDER_UV = 3 };
 struct GridFld {  // one Fourier-space field <-> one user grid field
   void *base;     // real_t array base; element (p) = base[((p/nproma)*nf_arr + fidx)*nproma + p%nproma]

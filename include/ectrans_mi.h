@@ -241,7 +241,7 @@ int emi_dir_transad(int kresol, const emi_dirtrans_t *args);
  * numbering of emi_setup; emi_inq_int(kresol, "ldlam") tells them apart.  INTEGRATION.md ("Limited-area transforms") defines the
  * transform; in short, per x-wavenumber m and n = 0 .. KNTMP(m) the spectral arrays hold four reals (a_r, a_i, b_r, b_i) with the field
  * index fastest, PSPEC(nfld, nspec2), and grid arrays hold the rows one after the other.
- * A limited-area handle serves emi_einv_trans, emi_edir_trans, emi_especnorm, emi_egpnorm, emi_edist_spec / emi_egath_spec /
+ * A limited-area handle serves emi_einv_trans, emi_edir_trans, emi_einv_transad, emi_edir_transad, emi_especnorm, emi_egpnorm, emi_edist_spec / emi_egath_spec /
  * emi_edist_grid / emi_egath_grid, the inquiries, emi_wait and emi_release; every spherical routine
  * returns EMI_ERR_UNSUPPORTED on it, and the two E-transforms return it on a handle of emi_setup.  NPRTRV > 1 is refused.
  * Further inquiries of such a handle -- emi_inq_int: "ldlam" "nmsmax" ("nsmax" is KSMAX) "ndgux"; emi_inq_int_array, all over
@@ -264,6 +264,23 @@ int emi_esetup(const emi_esetup_t *cfg, int *kresol);
  * are there.                                                                                                                       */
 int emi_einv_trans(int kresol, const emi_invtrans_t *args, const void *meanu, const void *meanv);
 int emi_edir_trans(int kresol, const emi_dirtrans_t *args, void *meanu, void *meanv);
+
+/* ---- EINV_TRANSAD / EDIR_TRANSAD (etrans/include/etrans/einv_transad.h, edir_transad.h) -------------------------------------------
+ * The transposes of emi_einv_trans (the means among its inputs) and of emi_edir_trans (the means among its outputs) for the inner
+ * products of the reference's own tests (tests/transi/transi_test_lam_invtrans_adjoint.c, ..._dirtrans_adjoint.c): plain sums over the
+ * NGPTOT points of every grid field of the call (the derivative, vorticity and divergence fields of the ld* flags included) and over
+ * the NSPEC2 reals of every spectral field plus the elements of PMEANU and PMEANV.  No SPECNORM-type weights, unlike the spherical
+ * adjoints.  Same argument blocks as the forward routines with the intents swapped: emi_einv_transad READS the gp* arrays and WRITES
+ * the sp* arrays and the means, emi_edir_transad reads sp* and the means and writes gp*.  Outputs are OVERWRITTEN (the reference adds
+ * to them; its callers zero them first).  emi_einv_transad writes exact zeros to the entries that do not enter emi_einv_trans (a_i, b_i
+ * of n = 0, b of m = 0); emi_edir_transad does not read the entries that emi_edir_trans writes as structural zeros.  With several
+ * tasks the task that owns m = 0 writes (reads) the means; the others leave them alone (ignore them).
+ * Limit: emi_einv_transad keeps u, v and the grid vorticity / divergence inputs of a wind field in one work array of the y-direction
+ * kernel; where KDGL is so large that the LDS (160 KiB) does not hold these 4 (ldvorgp) or 3 (lddivgp alone) columns the call returns
+ * EMI_ERR_UNSUPPORTED.  Calls without the two flags work for every KDGL that emi_esetup accepts.  INTEGRATION.md ("Limited-area
+ * adjoints") holds the closed forms.                                                                                                */
+int emi_einv_transad(int kresol, const emi_invtrans_t *args, void *meanu, void *meanv);
+int emi_edir_transad(int kresol, const emi_dirtrans_t *args, const void *meanu, const void *meanv);
 
 /* ---- ESPECNORM (etrans/include/etrans/especnorm.h; espnorm_ctl_mod.F90, espnormd_mod.F90) -----------------------------------------
  * PNORM(f) = sqrt( sum over m = 0 .. KMSMAX of S(f, m) ),  S(f, m) = sum over n = 0 .. KNTMP(m) of w(m, n) (a_r^2 + a_i^2 + b_r^2 + b_i^2)
