@@ -1944,6 +1944,20 @@ extern "C" int emi_inq_int_array(int kresol, const char *name, int *out, int len
     tmp.assign(P->ndgl, 0);
     for (int j = 0; j < P->nlat; j++) tmp[P->lat0 + j] = P->fplans[P->planid[j]].S;
     v = &tmp;
+  } else if (s == "fftplan") {  // [ndgl][5] what runs the FFT of every latitude of this task (0 elsewhere); diagnostic (tests check
+    // which plan a row length selects): kernel family -- 0 generic in-LDS, 1 specialised in-LDS (k_fft_*_hot), 2 register-resident
+    // (k_fft_*_r16), 3 split (k_fft_*_r16p), 4 direct mixed radix (k_fft_*_mr), 5 generic on global scratch (k_fft_*_gm) --, the
+    // mixed-radix factors A, B, C (1 where absent; 0 for the other families), fields per workgroup
+    tmp.assign((size_t)P->ndgl * 5, 0);
+    for (int j = 0; j < P->nlat; j++) {
+      const FftPlanDev &pl = P->fplans[P->planid[j]];
+      const FftClass &fc = P->fclass[pl.lds_class];
+      int *o = &tmp[(size_t)(P->lat0 + j) * 5];
+      o[0] = fc.mr ? 4 : fc.split ? 3 : fc.r16 ? 2 : fc.gmem ? 5 : fc.hot ? 1 : 0;
+      if (fc.mr) o[1] = pl.fac[0], o[2] = pl.fac[1], o[3] = pl.fac[2];
+      o[4] = pl.fbk;
+    }
+    v = &tmp;
   } else
     EMI_FAIL(EMI_ERR_ARG, "emi_inq_int_array: unknown name '%s'", s.c_str());
   if (len < (int)v->size()) EMI_FAIL(EMI_ERR_ARG, "TRANS_INQ: %s TOO SMALL (%d < %zu)", s.c_str(), len, v->size());
