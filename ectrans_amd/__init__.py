@@ -337,14 +337,15 @@ _INT_SCALARS = ("nspec2", "nspec2g", "nspec2mx", "nspec", "nspecg", "ngptot", "n
                 "nsmax", "ndlon", "nproc", "myproc", "nfrstlat", "nlstlat", "nprtrw", "nprtrv", "mysetw", "mysetv", "ngptot_band",
                 "ldll", "lshiftll")
 _INT_ARRAYS = {"nloen": "ndgl", "nmen": "ndgl", "ndglu": "nsmax+1", "nasm0": "nsmax+1", "myms": "nump",
-               "procm": "nsmax+1", "latlo": "nproc+1", "fftwork": "ndgl", "fftplan": "ndgl*5"}
+               "procm": "nsmax+1", "latlo": "nproc+1", "fftwork": "ndgl", "fftplan": "ndgl*5", "fftfac": "ndgl*15"}
 _REAL_ARRAYS = {"rmu": "ndgl", "pmu": "ndgl", "rgw": "ndgl", "pgw": "ndgl", "racthe": "ndgl"}
 
 
 def trans_inq(kresol, name):
-    """TRANS_INQ (trans_inq.h): one quantity by (lower-case) name.  Two diagnostics beside the reference's names: "fftwork" (per
-    latitude the work length of its FFT) and "fftplan" ((ndgl, 5): kernel family -- 0 generic, 1 specialised in place, 2 register-resident,
-    3 split, 4 direct mixed radix, 5 global scratch --, the mixed-radix factors A, B, C (0 for the other families), fields per workgroup)."""
+    """TRANS_INQ (trans_inq.h): one quantity by (lower-case) name.  Three diagnostics beside the reference's names: "fftwork" (per
+    latitude the work length of its FFT), "fftplan" ((ndgl, 5): kernel family -- 0 generic, 1 specialised in place, 2 register-resident,
+    3 split, 4 direct mixed radix, 5 global scratch --, the mixed-radix factors A, B, C (0 for the other families), fields per workgroup)
+    and "fftfac" ((ndgl, 15): the pass count and the factors of the FFT in pass order)."""
     L = lib()
     name = name.lower()
     if name in _INT_SCALARS:
@@ -353,11 +354,11 @@ def trans_inq(kresol, name):
         return v.value
     dims = {"ndgl": trans_inq(kresol, "ndgl"), "nsmax+1": trans_inq(kresol, "nsmax") + 1,
             "nump": trans_inq(kresol, "nump"), "nproc+1": trans_inq(kresol, "nproc") + 1}
-    dims["ndgl*5"] = dims["ndgl"] * 5
+    dims["ndgl*5"], dims["ndgl*15"] = dims["ndgl"] * 5, dims["ndgl"] * 15
     if name in _INT_ARRAYS:
         out = np.zeros(dims[_INT_ARRAYS[name]], dtype=np.int32)
         _chk(L.emi_inq_int_array(kresol, name.encode(), out.ctypes.data_as(C.POINTER(C.c_int)), out.size))
-        return out.reshape(-1, 5) if name == "fftplan" else out  # per latitude: family, A, B, C, fields per workgroup
+        return out.reshape(-1, 5) if name == "fftplan" else out.reshape(-1, 15) if name == "fftfac" else out  # per latitude: family, A, B, C, fields per workgroup; pass count, factors
     if name in _REAL_ARRAYS:
         out = np.zeros(dims[_REAL_ARRAYS[name]])
         _chk(L.emi_inq_real_array(kresol, name.encode(), out.ctypes.data_as(C.POINTER(C.c_double)), out.size))
@@ -678,7 +679,7 @@ def edir_transad(kresol, pspvor=None, pspdiv=None, pspscalar=None, pspsc3a=None,
 _E_INT_SCALARS = ("nspec", "nspec2", "nspec2g", "nspec2mx", "nump", "ngptot", "ngptotg", "ngptotmx", "nprtrw", "mysetw", "mysetv",
                   "nsmax", "nmsmax", "ndgl", "ndlon", "ndgux", "ldlam", "nfrstlat", "nlstlat", "nproc", "myproc")
 _E_INT_ARRAYS = {"myms": "nump", "kntmp": "m", "ncpl2m": "m", "ncpl4m": "m", "npme": "m", "nesm0": "m", "ndim0g": "m", "nallms": "m",
-                 "procm": "m", "numpp": "w", "nptrms": "w", "npossp": "w+1", "latlo": "w+1", "nloen": "ndgl", "fftwork": "ndgl", "fftplan": "ndgl*5"}
+                 "procm": "m", "numpp": "w", "nptrms": "w", "npossp": "w+1", "latlo": "w+1", "nloen": "ndgl", "fftwork": "ndgl", "fftplan": "ndgl*5", "fftfac": "ndgl*15"}
 
 
 def etrans_inq(kresol, name):
@@ -699,10 +700,10 @@ def etrans_inq(kresol, name):
         dims = {"nump": "nump", "ndgl": "ndgl"}
         k = _E_INT_ARRAYS[name]
         n = q("nmsmax") + 1 if k == "m" else q("nprtrw") if k == "w" else q("nprtrw") + 1 if k == "w+1" else \
-            5 * q("ndgl") if k == "ndgl*5" else q(dims[k])
+            5 * q("ndgl") if k == "ndgl*5" else 15 * q("ndgl") if k == "ndgl*15" else q(dims[k])
         out = np.zeros(n, dtype=np.int32)
         _chk(L.emi_inq_int_array(kresol, name.encode(), out.ctypes.data_as(C.POINTER(C.c_int)), out.size))
-        return out.reshape(-1, 5) if name == "fftplan" else out  # per row: family, A, B, C, fields per workgroup
+        return out.reshape(-1, 5) if name == "fftplan" else out.reshape(-1, 15) if name == "fftfac" else out  # per row: family, A, B, C, fields per workgroup; pass count, factors
     if name in ("rlepinm", "plepinm"):
         out = np.zeros(q("nspec2g") // 4)
         _chk(L.emi_inq_real_array(kresol, name.encode(), out.ctypes.data_as(C.POINTER(C.c_double)), out.size))

@@ -1958,6 +1958,17 @@ extern "C" int emi_inq_int_array(int kresol, const char *name, int *out, int len
       o[4] = pl.fbk;
     }
     v = &tmp;
+  } else if (s == "fftfac") {  // [ndgl][15] the factor list of the FFT of every latitude of this task (0 elsewhere): the pass count, then
+    // the factors in pass order (the register-resident and split kernels: R1 alone, their 16, 16 are compile-time); diagnostic (tests
+    // check which radix lands in which pass of the generic kernels, which walk this list at run time)
+    tmp.assign((size_t)P->ndgl * 15, 0);
+    for (int j = 0; j < P->nlat; j++) {
+      const FftPlanDev &pl = P->fplans[P->planid[j]];
+      int *o = &tmp[(size_t)(P->lat0 + j) * 15];
+      o[0] = pl.nfac;
+      for (int i = 0; i < pl.nfac; i++) o[1 + i] = pl.fac[i];
+    }
+    v = &tmp;
   } else
     EMI_FAIL(EMI_ERR_ARG, "emi_inq_int_array: unknown name '%s'", s.c_str());
   if (len < (int)v->size()) EMI_FAIL(EMI_ERR_ARG, "TRANS_INQ: %s TOO SMALL (%d < %zu)", s.c_str(), len, v->size());

@@ -29,16 +29,15 @@ the floor of 4 float32 epsilons on the denominator), adjoint identities at most 
 import numpy as np
 import pytest
 
-from tests import mr_cover
+from tests import mr_cover, plan_rows
 from tests.common import adjoint_case, run_case
 from tests.lam_ad_common import ALL, lam_ad_case
-from tests.lam_common import lam_case, units
 from tests.test_gpu_parity import MR_MID, MR_SHORT
 from tests.test_gpu_white_direct import check as sphere_white_check
-from tests.test_lam_gpu import TOL, mover, white_check
+from tests.plan_rows import KSMAX, NDGL, cut
+from tests.test_lam_gpu import TOL, mover
 
 pytestmark = pytest.mark.gpu
-NDGL, KSMAX = 12, 5
 LISTED = [(n, p) for p in (8, 4) for n in mr_cover.lengths(p)]
 IDS = ["%d-fp%d" % (n, 8 * p) for n, p in LISTED]
 
@@ -54,39 +53,17 @@ def et():
     ectrans_amd.trans_end()
 
 
-class Handle:
-    """a limited-area handle of NDGL rows of n points whose rows select the recorded plan of n"""
-
-    def __init__(self, et, n, precision, kmsmax=None):
-        self.et, self.n, self.precision = et, n, precision
-        self.M = (n - 1) // 2 if kmsmax is None else kmsmax
-
-    def __enter__(self):
-        exwn, eywn = units(self.n, NDGL)
-        self.r = self.et.esetup_trans(self.M, KSMAX, NDGL, kdlon=self.n, pexwn=exwn, peywn=eywn, precision=self.precision)
-        mr_cover.assert_plan(self.et.etrans_inq(self.r, "fftplan"), self.n, self.precision)
-        return self
-
-    def __exit__(self, *exc):
-        self.et.trans_release(self.r)
+def check(et, r, n, precision):
+    mr_cover.assert_plan(et.etrans_inq(r, "fftplan"), n, precision)
 
 
-def cut(n):
-    """an odd NPROMA smaller than the row: rows cross blocks and fields start on odd elements -- the copy into the LDS with the pad index
-    and the perm[] copy out of it"""
-    return 4093 if n > 4093 else n - 1
+def Handle(et, n, precision, kmsmax=None):
+    return plan_rows.Handle(et, n, precision, check, kmsmax)
 
 
 def forward(et, n, precision, nproma, what, kmsmax=None):
     """lam_case (winds, scalars, all four flags) and lam_white_case on one handle, under the bounds of tests/test_lam_gpu.py"""
-    to, back = mover("device", precision)
-    with Handle(et, n, precision, kmsmax) as h:
-        errs, _ = lam_case(et, n, NDGL, h.M, KSMAX, nproma=nproma, precision=precision, to_dev=to, to_host=back, kresol=h.r)
-        print("mr plan", what, n, mr_cover.plan_of(precision, n), "fp%d" % (8 * precision), "KMSMAX", h.M, "band-limited %.1e" % max(errs.values()))
-        assert max(errs.values()) < TOL[precision], errs
-        if precision == 4:
-            assert max(errs.values()) > 1e-9  # really computed in float
-        white_check(et, n, NDGL, h.M, KSMAX, "device", precision, "mr plan %s %d KMSMAX %d" % (what, n, h.M), nproma=nproma, kresol=h.r)
+    plan_rows.forward(et, n, precision, nproma, check, "mr plan %s %d %s" % (what, n, mr_cover.plan_of(precision, n)), kmsmax)
 
 
 def test_list_covers_the_plan_space_and_selects_the_recorded_plans(et):
