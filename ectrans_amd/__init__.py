@@ -21,7 +21,7 @@ import numpy as np
 
 __all__ = ["TransError", "setup_trans0", "setup_trans", "inv_trans", "dir_trans", "trans_inq", "specnorm",
            "trans_release", "trans_end", "lib", "build", "esetup_trans", "einv_trans", "edir_trans", "etrans_inq",
-           "einv_transad", "edir_transad"]
+           "einv_transad", "edir_transad", "fpbipere", "etibihie", "horiz_field", "boyd_window"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBPATH = os.path.join(_HERE, "libectrans_mi.so")
@@ -89,7 +89,7 @@ def build(force=False):
     """Compile libectrans_mi.so for gfx950 with hipcc (in-tree)."""
     import subprocess
     src = os.path.join(_HERE, "csrc", "ectrans_mi.hip")
-    deps = [src] + [os.path.join(_HERE, "csrc", f) for f in ("emi_kernels.h", "emi_kernels_body.h", "emi_mr_body.h", "emi_mr_tables.h", "emi_types.h", "emi_rt.h", "emi_setup.h", "emi_stage.h")]
+    deps = [src] + [os.path.join(_HERE, "csrc", f) for f in ("emi_kernels.h", "emi_kernels_body.h", "emi_mr_body.h", "emi_biper_body.h", "emi_mr_tables.h", "emi_types.h", "emi_rt.h", "emi_setup.h", "emi_stage.h")]
     deps.append(os.path.join(os.path.dirname(_HERE), "include", "ectrans_mi.h"))
     if not force and os.path.exists(_LIBPATH) and all(os.path.getmtime(_LIBPATH) >= os.path.getmtime(d) for d in deps):
         return _LIBPATH
@@ -169,6 +169,12 @@ def _bind(L):
         L.emi_egath_spec.argtypes = L.emi_gath_spec.argtypes
         L.emi_edist_grid.argtypes = L.emi_dist_grid.argtypes
         L.emi_egath_grid.argtypes = L.emi_gath_grid.argtypes
+    if hasattr(L, "emi_fpbipere"):  # (an older build loaded for an A/B run)
+        L.emi_fpbipere.argtypes = [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 9 + [ip, dp]
+        L.emi_etibihie.argtypes = [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 10
+        L.emi_boyd_window.argtypes = [C.c_int, C.c_double, C.c_int, C.c_void_p]
+        L.emi_horiz_field.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.emi_biper_last_ms.argtypes = [dp]
     return L
 
 
@@ -827,6 +833,70 @@ def vordiv_to_uv(pspvor, pspdiv, ksmax, pspu=None, pspv=None, mem_space=None):
         raise TransError("VORDIV_TO_UV: PSPVOR, PSPDIV, PSPU, PSPV must be [nspec2, nfld] arrays of one shape")
     _chk(lib().emi_vordiv_to_uv(int(ksmax), 8 if is64 else 4, _space(mem_space, space), pv_, pd_, pu_, pw_, int(pspvor.shape[1]), int(pspvor.shape[0])))
     return pspu, pspv
+
+
+# ---------------------------------------------------------------------------------------------
+# Biperiodicisation (etrans/cpu/biper): FPBIPERE, ETIBIHIE, HORIZ_FIELD.  No resolution handle, setup_trans0 only.
+# ---------------------------------------------------------------------------------------------
+def _biper_array(who, pgpbi, ndim):
+    name = str(pgpbi.dtype).replace("torch.", "")
+    if name not in ("float64", "float32") or pgpbi.ndim != ndim:
+        raise TransError("%s: PGPBI must be a %d-dimensional float64 or float32 array" % (who, ndim))
+    space = [None, name]
+    p, keep = _ptr(pgpbi, space)
+    return p, keep, space, 8 if name == "float64" else 4
+
+
+def fpbipere(pgpbi, kdlux, kdgux, kdlon, kdgl, ldzon=False, ldboyd=False, kdboyd=None, plboyd=None, mem_space=None, kdadd=0):
+    """FPBIPERE (biper/external/fpbipere.F90): the fields PGPBI(KD1, KNUBI) = ``pgpbi[knubi, kd1]``, known on C+I (kdlux x kdgux), are
+    made doubly periodic on C+I+E (kdlon x kdgl), in place.  ldzon: the C+I rows lie kdlon apart on input (else kdlux apart, packed);
+    on output they always lie kdlon apart.  ldboyd: Boyd's window with ``kdboyd`` (6 integers) and ``plboyd`` instead of spline and
+    smoothing.  A numpy array is staged, a torch tensor on the device is used in place; the precision is the array's dtype."""
+    p, keep, space, esz = _biper_array("FPBIPERE", pgpbi, 2)
+    kb = None if kdboyd is None else np.ascontiguousarray(kdboyd, dtype=np.int32)
+    if kb is not None and kb.size < 6:
+        raise TransError("FPBIPERE: KDBOYD must hold 6 integers")
+    pl = None if plboyd is None else C.c_double(float(plboyd))
+    _chk(lib().emi_fpbipere(_space(mem_space, space), esz, p, int(kdlux), int(kdgux), int(kdlon), int(kdgl), int(pgpbi.shape[0]), int(pgpbi.shape[1]),
+                            int(kdadd), int(bool(ldzon)), int(bool(ldboyd)), None if kb is None else kb.ctypes.data_as(C.POINTER(C.c_int)),
+                            None if pl is None else C.byref(pl)))
+    return pgpbi
+
+
+def etibihie(pgpbi, kdlon, kdgl, kdlux, kdgux, kstart, kdlsm, ldbix, ldbiy, mem_space=None, kdadd=0):
+    """ETIBIHIE (biper/external/etibihie.F90): the same on PGPBI(KSTART:KDLSM, KNUBI, KDGL) = ``pgpbi[kdgl, knubi, kdlsm - kstart + 1]``,
+    in place; ldbix / ldbiy switch the directions.  The columns outside 1 .. kdlon are not touched."""
+    p, keep, space, esz = _biper_array("ETIBIHIE", pgpbi, 3)
+    if int(pgpbi.shape[0]) != int(kdgl) or int(pgpbi.shape[2]) != int(kdlsm) - int(kstart) + 1:
+        raise TransError("ETIBIHIE: PGPBI must be [kdgl, knubi, kdlsm - kstart + 1] = [%d, :, %d]" % (kdgl, kdlsm - kstart + 1))
+    _chk(lib().emi_etibihie(_space(mem_space, space), esz, p, int(kdlon), int(kdgl), int(pgpbi.shape[1]), int(kdlux), int(kdgux), int(kstart), int(kdlsm),
+                            int(bool(ldbix)), int(bool(ldbiy)), int(kdadd)))
+    return pgpbi
+
+
+def horiz_field(kx, ky, dtype):
+    """HORIZ_FIELD (biper/external/horiz_field.F90): the test field PHFIELD(KX, KY) as a host array ``[ky, kx]``."""
+    out = np.zeros((int(ky), int(kx)), dtype=np.dtype(dtype))
+    if out.dtype not in (np.dtype("float64"), np.dtype("float32")):
+        raise TransError("HORIZ_FIELD: dtype must be float64 or float32")
+    _chk(lib().emi_horiz_field(int(kx), int(ky), out.dtype.itemsize, out.ctypes.data))
+    return out
+
+
+def boyd_window(n, scale, dtype):
+    """The weights b(1 .. n) of Boyd's window (ewindowe_mod.F90:107-131) in the precision ``dtype``, as the library computes them."""
+    out = np.zeros(int(n), dtype=np.dtype(dtype))
+    if out.dtype not in (np.dtype("float64"), np.dtype("float32")):
+        raise TransError("boyd_window: dtype must be float64 or float32")
+    _chk(lib().emi_boyd_window(int(n), float(scale), out.dtype.itemsize, out.ctypes.data))
+    return out
+
+
+def biper_last_ms():
+    """With set_profile(1): device ms of the last fpbipere / etibihie call by kernel (spline x, spline y, smoothing, band copy)."""
+    ms = (C.c_double * 4)()
+    _chk(lib().emi_biper_last_ms(ms))
+    return list(ms)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -3637,6 +3637,223 @@ extern "C" int emi_vordiv_to_uv(int ksmax, int precision, int mem_space, const v
   return rc;
 }
 
+// ------------------------------------------------------------------------------------------
+// Biperiodicisation: FPBIPERE, ETIBIHIE, HORIZ_FIELD (etrans/cpu/biper; kernels: emi_biper_body.h).  No resolution handle: the
+// routines act on whole fields of one task.  They run on the null stream behind the last transform of every resolution and return
+// when the device has finished; scratch memory is allocated per call and freed on every way out.
+// ------------------------------------------------------------------------------------------
+static int biper_begin() {
+  for (auto &p : G.plans)
+    if (p && plan_begin(*p, (emi_stream_t)0)) return -1;
+  return 0;
+}
+// With emi_set_profile(1) the kernels of a call are bracketed by events and emi_biper_last_ms gives the device time of the last call by
+// kernel: k_biper_spline_x, k_biper_spline_y, k_biper_smooth, k_biper_copy (tools/biper_rate.py).
+static double g_biper_ms[4] = {0.0, 0.0, 0.0, 0.0};
+struct BiperTimer {
+#ifndef EMI_CPU_EMU
+  std::vector<std::pair<hipEvent_t, int>> ev;  // (event, the kernel launched before it; -1: the start)
+  bool on;
+  BiperTimer() : on(G.profile != 0) { mark(-1); }
+  void mark(int k) {
+    if (!on) return;
+    hipEvent_t e;
+    if (hipEventCreate(&e) != hipSuccess) return;
+    (void)hipEventRecord(e, (hipStream_t)0);
+    ev.push_back({e, k});
+  }
+  ~BiperTimer() {  // (the stream has been synchronised)
+    if (on)
+      for (int k = 0; k < 4; k++) g_biper_ms[k] = 0.0;
+    for (size_t i = 0; i < ev.size(); i++) {
+      float ms = 0.f;
+      if (i > 0 && hipEventElapsedTime(&ms, ev[i - 1].first, ev[i].first) == hipSuccess) g_biper_ms[ev[i].second] += ms;
+    }
+    for (auto &e : ev) (void)hipEventDestroy(e.first);
+  }
+#else
+  void mark(int) {}
+#endif
+};
+extern "C" int emi_biper_last_ms(double *ms4) {
+  for (int k = 0; k < 4; k++) ms4[k] = g_biper_ms[k];
+  return EMI_SUCCESS;
+}
+// spline extension + smoothing of nf fields whose element (x, f, y), zero-based, is w[x + f sf + y sy] (ESPLINE, ESMOOTHE)
+static int biper_core(int esz, void *w, long long sf, long long sy, int X, int Y, int UX, int UY, int nf, bool bix, bool biy) {
+  const int EX = X - UX, EY = Y - UY;
+  int X1 = X, X2 = X, Y1 = Y, Y2 = Y;
+  if (bix && !biy) Y1 = Y2 = UY;
+  if (biy && !bix) X1 = X2 = UX;
+  const int iend = (std::max(EX, EY) + 1) / 2;
+  const size_t band_elems = (size_t)std::max((long long)(X1 - UX) * Y2, (long long)(Y1 - UY) * X2) * nf;
+  void *band = nullptr;
+  if (band_elems && emi_dev_malloc(&band, band_elems * esz)) return -1;
+  const emi_stream_t st = (emi_stream_t)0;
+  int rc;
+  {
+    BiperTimer tm;
+    if (bix && EX > 0) {
+      EMI_LAUNCH_P(esz, k_biper_spline_x, ((long long)EX * UY * nf + 255) / 256, 256, 0, st, (RT *)w, sf, sy, X, UX, UY, nf);
+      tm.mark(0);
+    }
+    if (biy && EY > 0) {
+      const int ncols = bix ? X : UX;
+      EMI_LAUNCH_P(esz, k_biper_spline_y, ((long long)ncols * nf + 255) / 256, 256, 0, st, (RT *)w, sf, sy, ncols, Y, UY, EX + 1, nf);
+      tm.mark(1);
+    }
+    for (int l = 1; l <= iend; l++) {
+      for (int half = 0; half < 2; half++) {
+        const int x0 = half ? 0 : UX + l - 1, nx = half ? X2 : (X1 - UX) - 2 * l + 2;
+        const int y0 = half ? UY + l - 1 : 0, ny = half ? (Y1 - UY) - 2 * l + 2 : Y2;
+        if (nx <= 0 || ny <= 0) continue;
+        const long long nblk = ((long long)nx * ny * nf + 255) / 256;
+        EMI_LAUNCH_P(esz, k_biper_smooth, nblk, 256, 0, st, (const RT *)w, sf, sy, X, Y, x0, nx, y0, ny, nf, (RT *)band);
+        tm.mark(2);
+        EMI_LAUNCH_P(esz, k_biper_copy, nblk, 256, 0, st, (RT *)w + x0 + (long long)y0 * sy, sf, sy, (const RT *)band, (long long)nx * ny, (long long)nx, nx, ny, nf);
+        tm.mark(3);
+      }
+    }
+    rc = emi_stream_sync(st);
+  }
+  emi_dev_free(band);
+  return rc;
+}
+static int biper_sizes(const char *who, int esz, int X, int Y, int UX, int UY, bool bix, bool biy, int kdadd) {
+  if (!G.init) EMI_FAIL(EMI_ERR_STATE, "%s: SETUP_TRANS0 has not been called", who);
+  if (esz != 8 && esz != 4) EMI_FAIL(EMI_ERR_ARG, "%s: element size %d (8 or 4)", who, esz);
+  if (kdadd != 0) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: KDADD = %d NOT SUPPORTED (the self-test of the externalised biperiodicisation changes the array shape)", who, kdadd);
+  if (X < 1 || Y < 1 || UX < 1 || UY < 1) EMI_FAIL(EMI_ERR_ARG, "%s: KDLON, KDGL, KDLUX, KDGUX = %d, %d, %d, %d MUST BE POSITIVE", who, X, Y, UX, UY);
+  if (UX > X || UY > Y) EMI_FAIL(EMI_ERR_ARG, "%s: KDLUX > KDLON OR KDGUX > KDGL (%d > %d, %d > %d)", who, UX, X, UY, Y);
+  if ((bix && UX < 2) || (biy && UY < 2))
+    EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: KDLUX = %d, KDGUX = %d: FEWER THAN 2 POINTS IN A PERIODICISED DIRECTION (the 2-D vertical-plane case is not supported)", who, UX, UY);
+  if (!bix && UX != X) EMI_FAIL(EMI_ERR_ARG, "%s: LDBIX = .FALSE. REQUIRES KDLUX = KDLON (%d, %d)", who, UX, X);
+  if (!biy && UY != Y) EMI_FAIL(EMI_ERR_ARG, "%s: LDBIY = .FALSE. REQUIRES KDGUX = KDGL (%d, %d)", who, UY, Y);
+  return 0;
+}
+
+/* The weights of Boyd's window (ewindowe_mod.F90:107-131) in the precision esz, on the host. */
+extern "C" int emi_boyd_window(int n, double scale, int esz, void *out) {
+  if (n < 0 || (esz != 8 && esz != 4) || (n > 0 && !out)) EMI_FAIL(EMI_ERR_ARG, "emi_boyd_window: bad arguments (n = %d, element size %d)", n, esz);
+  for (int j = 1; j <= n; j++) {
+    if (esz == 8) {
+      const double t = (double)(-n - 1 + 2 * j) / (double)(n + 1), l = t / std::sqrt(1.0 - (t * t));
+      ((double *)out)[j - 1] = (1.0 + std::erf(scale * l)) / 2.0;
+    } else {
+      const float t = (float)(-n - 1 + 2 * j) / (float)(n + 1), l = t / std::sqrt(1.0f - (t * t));
+      ((float *)out)[j - 1] = (1.0f + std::erf((float)scale * l)) / 2.0f;
+    }
+  }
+  return EMI_SUCCESS;
+}
+
+/* HORIZ_FIELD (biper/external/horiz_field.F90:67-73): the expression as Fortran types it -- default-real literals and integers with
+ * PPI, a JPRB parameter of the default-real value 3.141592.  esz = 4: all of it in float; esz = 8: (jx + 0.5 imax), (jy + 0.7 imax) and
+ * the literal 0.1 are float values, the rest is double. */
+extern "C" int emi_horiz_field(int kx, int ky, int esz, void *out) {
+  if (kx < 1 || ky < 1 || (esz != 8 && esz != 4) || !out) EMI_FAIL(EMI_ERR_ARG, "HORIZ_FIELD: bad arguments (KX = %d, KY = %d, element size %d)", kx, ky, esz);
+  const int imax = std::max(kx, ky);
+  for (int jy = 1; jy <= ky; jy++)
+    for (int jx = 1; jx <= kx; jx++) {
+      const float a = (float)jx + 0.5f * (float)imax, b = (float)jy + 0.7f * (float)imax;
+      const size_t i = (size_t)(jy - 1) * kx + (jx - 1);
+      if (esz == 8) {
+        const double ppi = (double)3.141592f;
+        ((double *)out)[i] = 280.0 * (1.0 + (double)0.1f * std::sin(ppi * (double)a * (double)b / (double)(imax * imax) + 1.0));
+      } else {
+        ((float *)out)[i] = 280.0f * (1.0f + 0.1f * std::sin(3.141592f * a * b / (float)(imax * imax) + 1.0f));
+      }
+    }
+  return EMI_SUCCESS;
+}
+
+extern "C" int emi_fpbipere(int mem_space, int esz, void *pgpbi, int kdlux, int kdgux, int kdlon, int kdgl, int knubi, int kd1, int kdadd, int ldzon, int ldboyd,
+                            const int *kdboyd, const double *plboyd) {
+  const char *who = "FPBIPERE";
+  const int X = kdlon, Y = kdgl, UX = kdlux, UY = kdgux;
+  if (int rc = biper_sizes(who, esz, X, Y, UX, UY, true, true, kdadd)) return rc;
+  int Wx = 0, Wy = 0;
+  long long need = (long long)X * Y;
+  if (ldboyd) {
+    if (!kdboyd) EMI_FAIL(EMI_ERR_ARG, "FPBIPERE: Boyd periodization requires KDBOYD argument");
+    if (!plboyd) EMI_FAIL(EMI_ERR_ARG, "FPBIPERE: Boyd periodization requires PLBOYD argument");
+    const int bwx = kdboyd[2], bwy = kdboyd[5];
+    if (bwx < 0 || bwy < 0) EMI_FAIL(EMI_ERR_ARG, "FPBIPERE: KDBOYD(3), KDBOYD(6) = %d, %d MUST NOT BE NEGATIVE", bwx, bwy);
+    Wx = 2 * bwx + (X - UX), Wy = 2 * bwy + (Y - UY);
+    if (X - UX != Y - UY)
+      EMI_FAIL(EMI_ERR_UNSUPPORTED,
+               "FPBIPERE: BOYD WINDOW WITH KDLON - KDLUX = %d /= KDGL - KDGUX = %d NOT SUPPORTED (EWINDOWE strides its rows by KDLUX + 2 (KBWX + KDGL - KDGUX): the row "
+               "length only where the two zones are equally wide)",
+               X - UX, Y - UY);
+    if (Wx > X || Wy > Y) EMI_FAIL(EMI_ERR_UNSUPPORTED, "FPBIPERE: BOYD WINDOW WIDER THAN THE DOMAIN (%d > %d OR %d > %d): THE BLENDED ZONES WOULD OVERLAP", Wx, X, Wy, Y);
+    need = (long long)(X + Wx) * (Y + Wy);
+    if (kd1 != need && knubi != 1)
+      EMI_FAIL(EMI_ERR_UNSUPPORTED, "FPBIPERE: BOYD WINDOW NEEDS KD1 = (KDLON + WX) (KDGL + WY) = %lld OR KNUBI = 1 (KD1 = %d: EWINDOWE re-declares PGPBI with that first extent)",
+               need, kd1);
+  }
+  if (kd1 < need) EMI_FAIL(EMI_ERR_ARG, "FPBIPERE: KD1 = %d TOO SMALL (%lld points are needed)", kd1, need);
+  if (knubi <= 0) return EMI_SUCCESS;
+  if (!pgpbi) EMI_FAIL(EMI_ERR_ARG, "FPBIPERE: PGPBI NOT PRESENT");
+  if (resolve_space(who, mem_space, {pgpbi}, &mem_space)) return EMI_ERR_ARG;
+  HostStage hs(esz);
+  if (biper_begin()) return EMI_ERR_RUNTIME;
+  void *d = hs.out(pgpbi, (size_t)kd1 * knubi, mem_space == EMI_MEM_HOST, true, 0);
+  if (hs.failed) EMI_FAIL(EMI_ERR_RUNTIME, "FPBIPERE: cannot stage the host array through device memory");
+  const emi_stream_t st = (emi_stream_t)0;
+  int rc = EMI_SUCCESS;
+  if (ldboyd) {
+    std::vector<char> bh((size_t)(Wx + Wy) * esz + 8);
+    emi_boyd_window(Wx, *plboyd, esz, bh.data());
+    emi_boyd_window(Wy, *plboyd, esz, bh.data() + (size_t)Wx * esz);
+    void *db = nullptr;
+    if (emi_dev_malloc(&db, bh.size()) || emi_h2d(db, bh.data(), bh.size(), st)) {
+      rc = EMI_ERR_RUNTIME;
+    } else {
+      const int ld = X + Wx, nrow = Y + Wy;
+      if (Wx > 0) EMI_LAUNCH_P(esz, k_biper_boyd, ((long long)Wx * nrow * knubi + 255) / 256, 256, 0, st, (RT *)d, (long long)kd1, ld, 0, X, Wx, nrow, knubi, (const RT *)db);
+      if (Wy > 0) EMI_LAUNCH_P(esz, k_biper_boyd, ((long long)Wy * ld * knubi + 255) / 256, 256, 0, st, (RT *)d, (long long)kd1, ld, 1, Y, Wy, ld, knubi, (const RT *)db + Wx);
+      if (emi_stream_sync(st)) rc = EMI_ERR_RUNTIME;
+    }
+    emi_dev_free(db);
+  } else {
+    if (!ldzon && UX != X) {  // the rows move from KDLUX to KDLON apart, in place: through a copy of C+I, as the reference's ZGPBI
+      void *c = nullptr;
+      const long long ci = (long long)UX * UY, nblk = (ci * knubi + 255) / 256;
+      if (emi_dev_malloc(&c, (size_t)ci * knubi * esz)) {
+        rc = EMI_ERR_RUNTIME;
+      } else {
+        EMI_LAUNCH_P(esz, k_biper_copy, nblk, 256, 0, st, (RT *)c, ci, (long long)UX, (const RT *)d, (long long)kd1, (long long)UX, UX, UY, knubi);
+        EMI_LAUNCH_P(esz, k_biper_copy, nblk, 256, 0, st, (RT *)d, (long long)kd1, (long long)X, (const RT *)c, ci, (long long)UX, UX, UY, knubi);
+        if (emi_stream_sync(st)) rc = EMI_ERR_RUNTIME;
+      }
+      emi_dev_free(c);
+    }
+    if (rc == EMI_SUCCESS && biper_core(esz, d, kd1, X, X, Y, UX, UY, knubi, true, true)) rc = EMI_ERR_RUNTIME;
+  }
+  if (rc == EMI_SUCCESS) hs.flush(st);
+  else emi_set_error("FPBIPERE: device memory or a launch failed");
+  return rc;
+}
+
+extern "C" int emi_etibihie(int mem_space, int esz, void *pgpbi, int kdlon, int kdgl, int knubi, int kdlux, int kdgux, int kstart, int kdlsm, int ldbix, int ldbiy,
+                            int kdadd) {
+  const char *who = "ETIBIHIE";
+  if (int rc = biper_sizes(who, esz, kdlon, kdgl, kdlux, kdgux, ldbix != 0, ldbiy != 0, kdadd)) return rc;
+  if (kstart > 1 || kdlsm < kdlon) EMI_FAIL(EMI_ERR_ARG, "ETIBIHIE: KSTART = %d > 1 OR KDLSM = %d < KDLON = %d: THE ROWS DO NOT HOLD 1 .. KDLON", kstart, kdlsm, kdlon);
+  if (knubi <= 0 || (!ldbix && !ldbiy)) return EMI_SUCCESS;
+  if (!pgpbi) EMI_FAIL(EMI_ERR_ARG, "ETIBIHIE: PGPBI NOT PRESENT");
+  if (resolve_space(who, mem_space, {pgpbi}, &mem_space)) return EMI_ERR_ARG;
+  const long long L = (long long)kdlsm - kstart + 1;
+  HostStage hs(esz);
+  if (biper_begin()) return EMI_ERR_RUNTIME;
+  void *d = hs.out(pgpbi, (size_t)L * knubi * kdgl, mem_space == EMI_MEM_HOST, true, 0);
+  if (hs.failed) EMI_FAIL(EMI_ERR_RUNTIME, "ETIBIHIE: cannot stage the host array through device memory");
+  if (biper_core(esz, (char *)d + (size_t)(1 - kstart) * esz, L, L * knubi, kdlon, kdgl, kdlux, kdgux, knubi, ldbix != 0, ldbiy != 0))
+    EMI_FAIL(EMI_ERR_RUNTIME, "ETIBIHIE: device memory or a launch failed");
+  hs.flush((emi_stream_t)0);
+  return EMI_SUCCESS;
+}
+
 extern "C" int emi_work_model(int kresol, int nfields, double *leg, double *fft, double *fbytes) {
   Plan *Pp = get_plan(kresol);
   if (!Pp) EMI_FAIL(EMI_ERR_STATE, "emi_work_model: unknown resolution %d", kresol);

@@ -3043,6 +3043,7 @@ EMI_KERNEL_LB2(256, EMI_R16P_WAVES) void k_fft_inv_r16p(EmiGeomDev g, FftTabDev 
 }
 
 #include "emi_mr_body.h"
+#include "emi_biper_body.h"
 
 // ==========================================================================================
 // k_gridcopy: TRLTOG / TRGTOL between the V-sets (NPRTRV > 1; trltog_mod.F90:18-964, trgtol_mod.F90:18-968).  Fourier space

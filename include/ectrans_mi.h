@@ -423,6 +423,33 @@ int emi_set_max_batch(int max_fields);
  * holds for any CRC; host memory only.                                                                    */
 int emi_crc64(const void *data, size_t bytes, unsigned long long *crc);
 
+/* ---- FPBIPERE / ETIBIHIE / HORIZ_FIELD (etrans/cpu/biper; INTEGRATION.md, "Biperiodicisation") ------------------------------
+ * A field known on the physical domain C+I (KDLUX x KDGUX points) is made doubly periodic on C+I+E (KDLON x KDGL): the extension
+ * zone E is filled by a cubic spline along x, then along y, and smoothed by a 9-point stencil, or Boyd's window blends the two
+ * sides.  The results are the reference's CPU routines' to the last bit in both precisions (no fused multiply-add, the reference's
+ * order of operations, its use of the x direction's lambda in the y pass included).
+ * The routines need emi_init only.  esz = bytes per real (8 | 4).  pgpbi: host or device memory (mem_space as everywhere: device
+ * arrays in place, host arrays staged whole); the call runs on the null stream behind the last transform of every resolution and
+ * returns when it has finished.  The input values of E are never read; nothing outside C+I+E (the tail of KD1, guard columns,
+ * further fields) is written.  A refused call (EMI_ERR_ARG / EMI_ERR_UNSUPPORTED) leaves the array as it was: kdadd != 0; fewer than
+ * 2 points of C+I in a periodicised direction; KDLUX > KDLON or KDGUX > KDGL; a direction switched off whose sizes differ; KD1 too
+ * small; KSTART > 1 or KDLSM < KDLON; Boyd's window without kdboyd / plboyd, with zones of different width, with a window wider
+ * than the domain, or with KD1 /= (KDLON + WX)(KDGL + WY) and more than one field.
+ * emi_fpbipere: PGPBI(KD1, KNUBI).  ldzon != 0: the C+I rows lie KDLON apart on input, else KDLUX apart (packed); on output KDLON.
+ *   ldboyd != 0: Boyd's window instead, WX = 2 kdboyd[2] + KDLON - KDLUX, WY = 2 kdboyd[5] + KDGL - KDGUX, rows of KDLON + WX
+ *   points, KDGL + WY rows; kdboyd (6 integers) and plboyd are host pointers, NULL = the argument is absent.
+ * emi_etibihie: PGPBI(KSTART:KDLSM, KNUBI, KDGL), either direction can be switched off.
+ * emi_boyd_window: out (host, n reals of esz bytes) = the weights b(1..n) of a window of n points with parameter `scale`.
+ * emi_horiz_field: out (host, PHFIELD(KX, KY) of esz bytes) = the test field of the reference's periodicisation test.           */
+int emi_fpbipere(int mem_space, int esz, void *pgpbi, int kdlux, int kdgux, int kdlon, int kdgl, int knubi, int kd1, int kdadd, int ldzon, int ldboyd,
+                 const int *kdboyd, const double *plboyd);
+int emi_etibihie(int mem_space, int esz, void *pgpbi, int kdlon, int kdgl, int knubi, int kdlux, int kdgux, int kstart, int kdlsm, int ldbix, int ldbiy, int kdadd);
+int emi_boyd_window(int n, double scale, int esz, void *out);
+int emi_horiz_field(int kx, int ky, int esz, void *out);
+/* With emi_set_profile(1): the device time (ms) of the last emi_fpbipere / emi_etibihie call by kernel -- spline along x, spline along y,
+ * the smoothing half-passes, the copies of their bands back into the field.                                                    */
+int emi_biper_last_ms(double *ms4);
+
 #ifdef __cplusplus
 }
 #endif
