@@ -169,6 +169,10 @@ def _bind(L):
         L.emi_egath_spec.argtypes = L.emi_gath_spec.argtypes
         L.emi_edist_grid.argtypes = L.emi_dist_grid.argtypes
         L.emi_egath_grid.argtypes = L.emi_gath_grid.argtypes
+    if hasattr(L, "emi_specnorm_met"):  # (an older build loaded for an A/B run)
+        L.emi_specnorm_met.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, dp]
+        L.emi_specnorm_met_partial.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, dp]
+        L.emi_specnorm_last_ms.argtypes = [dp]
     if hasattr(L, "emi_fpbipere"):  # (an older build loaded for an A/B run)
         L.emi_fpbipere.argtypes = [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 9 + [ip, dp]
         L.emi_etibihie.argtypes = [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 10
@@ -760,12 +764,15 @@ def egpnorm_trans(kresol, pgp, kfields=None, kproma=None, ldave_only=False, pmin
     return _gpnorm("emi_egpnorm", kresol, pgp, kfields, kproma, ldave_only, pmin, pmax, mem_space)
 
 
-def specnorm(kresol, pspec, kvset=None, mem_space=None):
+def specnorm(kresol, pspec, kvset=None, mem_space=None, pmet=None):
     """SPECNORM (specnorm.h:12): per-field spectral L2 norm, returned as a numpy array (on every
     task; the reference returns it on the master only).  kvset (NPRTRV > 1, specnorm.F90:82-101): V-set of every GLOBAL
     field; pspec holds this task's fields of its own V-set and the norms of all len(kvset) fields come back.
     mem_space: overrides the memory space derived from the arrays (EMI_MEM_AUTO; on the CPU emulator of the tests EMI_MEM_DEVICE uses
-    numpy arrays in place, the path device tensors take on a GPU)."""
+    numpy arrays in place, the path device tensors take on a GPU).
+    pmet: the metric PMET(0:NSMAX), a host array of at least NSMAX + 1 elements read from element n = 0 (spnormd_mod.F90):
+    PNORM(f)^2 = sum over m of c_m sum over n of pmet[n] (re^2 + im^2).  Several tasks: the library gathers the per-wavenumber sums
+    over the host collectives, and the norms are the bytes of one task."""
     space = [None, real_dtype(kresol)]
     if pspec.shape[1] == 0:
         p, keep, space[0] = None, None, EMI_MEM_HOST
@@ -773,6 +780,15 @@ def specnorm(kresol, pspec, kvset=None, mem_space=None):
         p, keep = _ptr(pspec, space)
         space[0] = _space(mem_space, space)
     pd = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    if pmet is not None:  # a small host array, whatever memory the fields live in
+        met = np.ascontiguousarray(_np(pmet), dtype=space[1]).reshape(-1)
+        kv = None
+        if kvset is not None and _DIST.get("nprtrv", 1) > 1:
+            kv = np.ascontiguousarray(kvset, dtype=np.int32)
+        out = np.zeros(pspec.shape[1] if kv is None else kv.size)
+        _chk(lib().emi_specnorm_met(kresol, space[0], p, pspec.shape[1], met.ctypes.data, met.size,
+                                    None if kv is None else kv.ctypes.data_as(C.POINTER(C.c_int)), 0 if kv is None else kv.size, pd(out)))
+        return out
     if kvset is not None and _DIST.get("nprtrv", 1) > 1:
         kv = np.ascontiguousarray(kvset, dtype=np.int32)
         out = np.zeros(kv.size)
@@ -786,6 +802,26 @@ def specnorm(kresol, pspec, kvset=None, mem_space=None):
     from . import dist as _dist
     _chk(lib().emi_specnorm_partial(kresol, space[0], p, pspec.shape[1], pd(out)))
     return np.sqrt(_dist.all_reduce_sum(out, _DIST["group"], _DIST["device"]))  # every task gets the norms
+
+
+def specnorm_met_partial(kresol, pspec, pmet, mem_space=None):
+    """emi_specnorm_met_partial: (nump, nfld) sums of this task's zonal wavenumbers, in MYMS order, c_m and the metric applied;
+    arguments as ``specnorm`` with pmet.  Needs no collectives: sum over m (and tasks) and take the root."""
+    space = [None, real_dtype(kresol)]
+    p, keep = _ptr(pspec, space)
+    space[0] = _space(mem_space, space)
+    met = np.ascontiguousarray(_np(pmet), dtype=space[1]).reshape(-1)
+    out = np.zeros((trans_inq(kresol, "nump"), int(pspec.shape[1])))
+    _chk(lib().emi_specnorm_met_partial(kresol, space[0], p, int(pspec.shape[1]), met.ctypes.data, met.size,
+                                        out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def specnorm_last_ms():
+    """emi_specnorm_last_ms: with ``set_profile(1)``, the device time (ms) of the kernel alone of the last ``specnorm`` call."""
+    v = C.c_double(0.0)
+    _chk(lib().emi_specnorm_last_ms(C.byref(v)))
+    return v.value
 
 
 def gpnorm_trans(kresol, pgp, kfields=None, kproma=None, ldave_only=False, pmin=None, pmax=None, mem_space=None):

@@ -355,6 +355,8 @@ struct Plan {  // owns its device memory; whoever drops a plan that has run some
   size_t cap_desc = 0;
   char *d_fftscr = nullptr;  // work arrays of the rows that exceed the LDS (k_fft_*_gm)
   size_t cap_fftscr = 0;
+  void *d_normws = nullptr;  // SPECNORM with PMET: the per-wavenumber sums and the metric of one call (calls end synchronised)
+  size_t cap_normws = 0;
   // Calls on one resolution share d_desc, W and the Fourier buffers, whatever stream each call names: every call
   // starts by making its stream wait for the event the previous call of this resolution recorded at its end.
 #ifndef EMI_CPU_EMU
@@ -372,6 +374,7 @@ Plan::~Plan() {
   if (d_FBF != d_FBL) emi_dev_free(d_FBF);
   emi_dev_free(d_desc);
   emi_dev_free(d_fftscr);
+  emi_dev_free(d_normws);
 }
 
 static int roundup(int a, int b) { return (a + b - 1) / b * b; }
@@ -3271,8 +3274,39 @@ static int wset_transform(Plan &P, const Call &c, bool inverse, bool adj, const 
   return EMI_SUCCESS;
 }
 
+// With emi_set_profile(1) the kernel of a SPECNORM call (k_specnorm, k_specnorm_met) is bracketed by events on the null stream, and
+// emi_specnorm_last_ms gives the device time of the last call's kernel alone (tools/specnorm_met_rate.py).
+static double g_specnorm_ms = 0.0;
+struct SpecnormTimer {
+#ifndef EMI_CPU_EMU
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  void start() {
+    if (G.profile == 0 || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return;
+    (void)hipEventRecord(e0, (hipStream_t)0);
+  }
+  void stop() {
+    if (e1) (void)hipEventRecord(e1, (hipStream_t)0);
+  }
+  ~SpecnormTimer() {  // (the stream has been synchronised)
+    float ms = 0.f;
+    if (e1 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) g_specnorm_ms = ms;
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+#else
+  void start() {}
+  void stop() {}
+#endif
+};
+extern "C" int emi_specnorm_last_ms(double *ms) {
+  if (!ms) EMI_FAIL(EMI_ERR_ARG, "emi_specnorm_last_ms: bad arguments");
+  *ms = g_specnorm_ms;
+  return EMI_SUCCESS;
+}
+
 static int specnorm_sumsq(Plan &P, int mem_space, const void *spec, int nfld, double *sumsq) {
   if (resolve_space("SPECNORM", mem_space, {spec}, &mem_space)) return EMI_ERR_ARG;
+  SpecnormTimer tm;
   HostStage hs(P.esz);
   // SPECNORM has no stream argument: it runs on the null stream behind the last transform of this resolution
   // (which may have been queued on a non-blocking stream, e.g. the DIR_TRANS that produced `spec`)
@@ -3281,7 +3315,9 @@ static int specnorm_sumsq(Plan &P, int mem_space, const void *spec, int nfld, do
   if (hs.failed) EMI_FAIL(EMI_ERR_RUNTIME, "SPECNORM: cannot stage the host array through device memory");
   void *d_out = nullptr;
   if (emi_dev_malloc(&d_out, (size_t)nfld * 8)) return EMI_ERR_RUNTIME;
+  tm.start();
   EMI_LAUNCH_P(P.esz, k_specnorm, nfld, 256, 256 * 8, (emi_stream_t)0, P.g, (long long)P.nspec2, (const RT *)d_sp, nfld, (double *)d_out);
+  tm.stop();
   emi_d2h(sumsq, d_out, (size_t)nfld * 8, 0);
   emi_stream_sync(0);
   emi_dev_free(d_out);
@@ -3399,6 +3435,124 @@ extern "C" int emi_specnorm_partial(int kresol, int mem_space, const void *spec,
   if (Pp->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): this routine serves the spherical transforms only", "SPECNORM", kresol);
   if (!spec || nfld <= 0 || !sumsq) EMI_FAIL(EMI_ERR_ARG, "SPECNORM: bad arguments");
   return specnorm_sumsq(*Pp, mem_space, spec, nfld, sumsq);
+}
+
+// SPECNORM with PMET (specnorm.h:12, spnorm_ctl_mod.F90, spnormd_mod.F90:36-53): the metric PMET(0:NSMAX) weights the coefficients of
+// total wavenumber n.  sums[ml][f], ml over this task's wavenumbers in MYMS order: k_specnorm_met.  pmet: host array of the handle's
+// precision with at least NSMAX + 1 elements; it is small and is uploaded with every call.  The unweighted call keeps k_specnorm.
+static int specnorm_met_check(int kresol, const void *pmet, int npmet, Plan **Pp) {
+  Plan *P = get_plan(kresol);
+  if (!P) EMI_FAIL(EMI_ERR_STATE, "SPECNORM: unknown resolution %d", kresol);
+  if (P->lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): this routine serves the spherical transforms only", "SPECNORM", kresol);
+  if (P->ldll) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: not available on a handle set up with LDLL (it serves INV_TRANS with LDLATLON only)", "SPECNORM with PMET");
+  if (!pmet) EMI_FAIL(EMI_ERR_ARG, "SPECNORM: PMET NOT PRESENT");
+  if (npmet < P->nsmax + 1) EMI_FAIL(EMI_ERR_ARG, "SPECNORM: PMET TOO SMALL (%d elements, %d are needed)", npmet, P->nsmax + 1);
+  *Pp = P;
+  return 0;
+}
+static int specnorm_met_sums(Plan &P, int mem_space, const void *spec, int nfld, const void *pmet, double *sums) {
+  if (resolve_space("SPECNORM", mem_space, {spec}, &mem_space)) return EMI_ERR_ARG;
+  if (P.nump == 0 || nfld == 0) return EMI_SUCCESS;
+  SpecnormTimer tm;
+  HostStage hs(P.esz);
+  if (plan_begin(P, (emi_stream_t)0)) return EMI_ERR_RUNTIME;  // the null stream, behind the last transform of this resolution (SPECNORM)
+  const void *d_sp = hs.in(spec, (size_t)P.nspec2 * nfld, mem_space == EMI_MEM_HOST, 0);
+  if (hs.failed) EMI_FAIL(EMI_ERR_RUNTIME, "SPECNORM: cannot stage the host array through device memory");
+  // the sums and the metric live in one buffer of the plan, grown on demand: every call ends synchronised, so the next one may reuse it
+  const size_t nout = (size_t)P.nump * nfld, nmet = (size_t)P.nsmax + 1, need = nout * 8 + nmet * P.esz;
+  if (need > P.cap_normws) {
+    emi_dev_free(P.d_normws);
+    P.d_normws = nullptr, P.cap_normws = 0;
+    if (emi_dev_malloc(&P.d_normws, need)) return EMI_ERR_RUNTIME;
+    P.cap_normws = need;
+  }
+  void *d_out = P.d_normws, *d_met = (char *)P.d_normws + nout * 8;
+  int rc = EMI_SUCCESS;
+  if (emi_h2d(d_met, pmet, nmet * P.esz, 0)) {
+    rc = EMI_ERR_RUNTIME;
+  } else {
+    const int ntile = (nfld + 63) / 64;
+    tm.start();
+    EMI_LAUNCH_P(P.esz, k_specnorm_met, (long long)P.nump * ntile, 256, 3 * 64 * 8, (emi_stream_t)0, P.g.mval, P.g.nasm0, P.nsmax, ntile, (const RT *)d_sp, nfld,
+                 (const RT *)d_met, (double *)d_out);
+    tm.stop();
+    if (emi_d2h(sums, d_out, nout * 8, 0)) rc = EMI_ERR_RUNTIME;
+  }
+  if (emi_stream_sync(0)) rc = EMI_ERR_RUNTIME;  // (also: the caller's pmet has been read)
+  return rc;
+}
+extern "C" int emi_specnorm_met_partial(int kresol, int mem_space, const void *spec, int nfld, const void *pmet, int npmet, double *sums) {
+  Plan *Pp = nullptr;
+  if (int rc = specnorm_met_check(kresol, pmet, npmet, &Pp)) return rc;
+  if (!spec || nfld <= 0 || !sums) EMI_FAIL(EMI_ERR_ARG, "SPECNORM: bad arguments");
+  return specnorm_met_sums(*Pp, mem_space, spec, nfld, pmet, sums);
+}
+// The per-wavenumber sums of all tasks are gathered and added for m = 0 .. NSMAX in ascending order on every task, as ESPECNORM does:
+// the norms do not depend on the number of W-set tasks, and every task gets them.  kvset == NULL: spec holds the nfld fields whose
+// norms are wanted (nfld_g is not read).  With kvset (NPRTRV > 1), as emi_specnorm_kvset: spec holds this V-set's fields, norms the
+// nfld_g norms of all fields; wavenumber m of a field of V-set v comes from the task (W-set of m, v).
+extern "C" int emi_specnorm_met(int kresol, int mem_space, const void *spec, int nfld, const void *pmet, int npmet, const int *kvset, int nfld_g, double *norms) {
+  Plan *Pp = nullptr;
+  if (int rc = specnorm_met_check(kresol, pmet, npmet, &Pp)) return rc;
+  Plan &P = *Pp;
+  if (!kvset) nfld_g = nfld;
+  if (nfld < 0 || nfld_g < 0 || (nfld > 0 && !spec) || (nfld_g > 0 && !norms) || (nfld == 0 && P.nprv == 1)) EMI_FAIL(EMI_ERR_ARG, "SPECNORM: bad arguments");
+  if (kvset) {
+    int mine = 0;
+    for (int f = 0; f < nfld_g; f++) {
+      if (kvset[f] < 1 || kvset[f] > P.nprv) EMI_FAIL(EMI_ERR_ARG, "SPECNORM:KVSET CONTAINS VALUES OUTSIDE RANGE");
+      mine += kvset[f] == P.mev + 1;
+    }
+    if (mine != nfld) EMI_FAIL(EMI_ERR_ARG, "SPECNORM: %d fields of KVSET belong to this V-set, PSPEC holds %d", mine, nfld);
+  }
+  const int NW = P.nproc, NV = P.nprv, NA = NW * NV, M = P.nsmax;
+  if (NA > 1 && !G.hc_gather)
+    EMI_FAIL(EMI_ERR_STATE, "SPECNORM: several tasks and no host collectives (emi_set_host_collectives): use emi_specnorm_met_partial and gather the sums");
+  std::vector<double> mine((size_t)std::max(P.nump, 1) * std::max(nfld, 1), 0.0), all;
+  if (int rc = specnorm_met_sums(P, mem_space, spec, nfld, pmet, mine.data())) return rc;
+  std::vector<int> lidx(M + 1, 0), numpp(NW, 0);
+  for (int m = 0; m <= M; m++) lidx[m] = numpp[P.procm[m]]++;
+  // task t = w * NPRTRV + v (specnorm_vsets); the V-sets may hold different numbers of fields: field counts first, then the sums
+  std::vector<long long> nf_all(NA, nfld), cnt(NA, 0), dsp(NA, 0);
+  const double *base = mine.data();
+  if (NA > 1) {
+    const int me = NV > 1 ? G.myproc_all - 1 : P.me;
+    if (NV > 1) {
+      std::vector<long long> one(NA, 8), d1(NA);
+      for (int t = 0; t < NA; t++) d1[t] = 8LL * t;
+      long long nf = nfld;
+      if (G.hc_gather(G.hc_user, &nf, 8, nf_all.data(), one.data(), d1.data(), NA)) EMI_FAIL(EMI_ERR_RUNTIME, "SPECNORM: all-gather-v failed");
+    }
+    long long tot = 0;
+    for (int t = 0; t < NA; t++) cnt[t] = 8LL * numpp[t / NV] * nf_all[t], dsp[t] = tot, tot += cnt[t];
+    all.resize((size_t)(tot / 8) + 1);
+    if (G.hc_gather(G.hc_user, mine.data(), cnt[me], all.data(), cnt.data(), dsp.data(), NA)) EMI_FAIL(EMI_ERR_RUNTIME, "SPECNORM: all-gather-v failed");
+    base = all.data();
+  }
+  // the squared norm of field k of V-set v
+  auto sumsq = [&](int v, long long k) {
+    double s = 0.0;
+    for (int m = 0; m <= M; m++) {
+      const int t = P.procm[m] * NV + v;
+      s += base[(size_t)(dsp[t] / 8) + (size_t)lidx[m] * (size_t)nf_all[t] + (size_t)k];
+    }
+    return s;
+  };
+  for (int v = 0; v < NV; v++)
+    for (int w = 1; w < NW; w++)
+      if (nf_all[w * NV + v] != nf_all[v])
+        EMI_FAIL(EMI_ERR_ARG, "SPECNORM: tasks %d and %d of V-set %d pass %lld and %lld fields", v + 1, w * NV + v + 1, v + 1, nf_all[v], nf_all[w * NV + v]);
+  if (!kvset) {
+    for (int f = 0; f < nfld; f++) norms[f] = std::sqrt(sumsq(NV > 1 ? P.mev : 0, f));
+    return EMI_SUCCESS;
+  }
+  std::vector<long long> k(NV, 0);
+  for (int f = 0; f < nfld_g; f++) {
+    const int v = kvset[f] - 1;
+    if (k[v] >= nf_all[v]) EMI_FAIL(EMI_ERR_ARG, "SPECNORM: V-set %d passed fewer fields than KVSET names", v + 1);
+    norms[f] = std::sqrt(sumsq(v, k[v]++));
+  }
+  return EMI_SUCCESS;
 }
 
 // ESPECNORM (etrans/cpu/external/especnorm.F90, internal/espnorm_ctl_mod.F90, espnormd_mod.F90): the spectral norms of a limited-area

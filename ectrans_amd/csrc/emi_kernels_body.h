@@ -3273,6 +3273,61 @@ EMI_KERNEL_LB(256) void k_especnorm(const int *kntmp, const int *nesm0, const in
 }
 
 // ==========================================================================================
+// k_specnorm_met: SPNORMD with a metric (spnormd_mod.F90:36-53, PMET(0:NSMAX) indexed by n): for local zonal wavenumber ml and field f
+//   out[ml][f] = c_m * sum over n = m .. NSMAX of PMET(n) (re^2 + im^2),   c_0 = 1 (real parts only), c_m = 2 for m > 0,
+// the pair of (m, n) at NASM0(m) + 2 (n - m) of PSPEC(nfld, nspec2); pmet (zero-based) and the inputs convert to double exactly, every
+// sum is in double.  Shaped like k_especnorm: one workgroup of 256 threads per (ml, tile of 64 fields), lane = field, a wave reads
+// rows of 64 consecutive reals.  Wave w walks n - m in [w K / 4, (w + 1) K / 4), K = NSMAX - m + 1, in ascending order, eight n (16 row
+// loads) in flight; the four partial sums are added in wave order and the factor 2 is exact.  The summation tree of one (m, f)
+// therefore depends on NSMAX - m alone: not on nfld, the field's position, the number of tasks or the owner of m.
+// ==========================================================================================
+EMI_KERNEL_LB(256) void k_specnorm_met(const int *mval, const int *nasm0, int nsmax, int ntile, const real_t *sp, int nfld, const real_t *pmet,
+                                       double *out /* [nump][nfld] */) {
+  EMI_FP_STRICT();
+  EMI_LDS_DECL;
+  double *red = (double *)EMI_LDS_PTR;  // [3][64]
+  const int ml = EMI_BID / ntile, tile = EMI_BID - ml * ntile;
+  const int lane = EMI_TID & 63, w = EMI_TID >> 6;
+  const int f = tile * 64 + lane;
+  const int m = mval[ml], K = nsmax - m + 1;
+  const int k0 = (w * K) >> 2, k1 = ((w + 1) * K) >> 2;
+  const bool zonal = m == 0;  // imaginary parts of m = 0 carry no weight, whatever the caller left in them
+  double s = 0.0;
+  if (f < nfld) {
+    const real_t *p = sp + ((long long)nasm0[ml] + 2LL * k0) * nfld + f;
+    const real_t *wm = pmet + m + k0;
+    int k = k0;
+    for (; k + 8 <= k1; k += 8) {
+      real_t v[16];
+#pragma unroll
+      for (int i = 0; i < 16; i++) v[i] = p[(long long)i * nfld];
+      double wt[8];
+#pragma unroll
+      for (int j = 0; j < 8; j++) wt[j] = (double)wm[j];
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        const double a = (double)v[2 * j], b = zonal ? 0.0 : (double)v[2 * j + 1];
+        s += wt[j] * (a * a + b * b);
+      }
+      p += 16LL * nfld;
+      wm += 8;
+    }
+    for (; k < k1; k++) {
+      const double a = (double)p[0], b = zonal ? 0.0 : (double)p[nfld];
+      s += (double)wm[0] * (a * a + b * b);
+      p += 2LL * nfld;
+      wm += 1;
+    }
+  }
+  if (w > 0) red[(w - 1) * 64 + lane] = s;
+  EMI_SYNC();
+  if (w == 0 && f < nfld) {
+    const double t = ((s + red[lane]) + red[64 + lane]) + red[128 + lane];
+    out[(long long)ml * nfld + f] = zonal ? t : 2.0 * t;
+  }
+}
+
+// ==========================================================================================
 // k_vd2uv: VORDIV_TO_UV (cpu/external/vordiv_to_uv.F90 -> cpu/internal/vd2uv_mod.F90:79-120 = PRFI1B + VDTUV, vdtuv_mod.F90:97-143):
 //   U_n = i m L_n D_n + (n-1) e_n L_(n-1) vor_(n-1) - (n+2) e_(n+1) L_(n+1) vor_(n+1)
 //   V_n = i m L_n vor_n - (n-1) e_n L_(n-1) D_(n-1) + (n+2) e_(n+1) L_(n+1) D_(n+1),   L_n = RLAPIN(n) = -a^2 / (n (n+1)),

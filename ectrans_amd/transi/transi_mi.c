@@ -93,6 +93,30 @@ int trans_new(struct Trans_t *t) {
   t->nsmax = -1;
   t->lsplit = 1;
   t->flt = -1;
+  t->llam = 0;
+  t->nmsmax = -1;
+  t->ndgux = -1;
+  t->pexwn = t->peywn = 1.0;
+  return TRANS_SUCCESS;
+}
+
+/* transi.c:116-142: a plane grid of ny rows of nx points with cells of dx x dy; the truncation in x and in y */
+int trans_set_resol_lam(struct Trans_t *t, int nx, int ny, double dx, double dy) {
+  const double two_pi = 6.283185307179586476925286766559;
+  if (nx <= 0 || ny <= 0 || !(dx > 0.0) || !(dy > 0.0)) return TRANS_ERROR;
+  free(t->nloen);
+  t->nloen = NULL;
+  t->ndgl = ny;
+  t->nlon = nx;
+  t->pexwn = two_pi / ((double)nx * dx);
+  t->peywn = two_pi / ((double)ny * dy);
+  t->llam = 1;
+  return TRANS_SUCCESS;
+}
+int trans_set_trunc_lam(struct Trans_t *t, int trunc_x, int trunc_y) {
+  t->llam = 1;
+  t->nmsmax = trunc_x;
+  t->nsmax = trunc_y;
   return TRANS_SUCCESS;
 }
 
@@ -142,9 +166,66 @@ int trans_set_cache(struct Trans_t *t, const void *cache, size_t cachesize) {
   return TRANS_SUCCESS;
 }
 
+static void fill_sizes(struct Trans_t *t) {
+  t->myproc = t->nproc = 1;
+  emi_inq_tasks(&t->nproc, &t->myproc);
+  emi_inq_int(t->handle, "nspec2", &t->nspec2);
+  t->nspec = t->nspec2 / 2;
+  emi_inq_int(t->handle, "nspec2g", &t->nspec2g);
+  emi_inq_int(t->handle, "nspec2mx", &t->nspec2mx);
+  emi_inq_int(t->handle, "nump", &t->nump);
+  emi_inq_int(t->handle, "ngptot", &t->ngptot);
+  emi_inq_int(t->handle, "ngptotg", &t->ngptotg);
+  emi_inq_int(t->handle, "ngptotmx", &t->ngptotmx);
+}
+
+/* a limited-area handle: ESETUP_TRANS with one row length (transi_module.F90:1050-1100) */
+static int setup_lam(struct Trans_t *t) {
+  if (t->ndgl <= 0 || t->nlon <= 0) return TRANS_MISSING_ARG;
+  if (t->nmsmax < 0) {
+    fprintf(stderr, "trans_setup: ERROR: nmsmax < 0\n");
+    return TRANS_ERROR;
+  }
+  if (t->llatlon) {
+    fprintf(stderr, "trans_setup: ERROR: a limited-area handle cannot be a lonlat handle\n");
+    return TRANS_ERROR;
+  }
+  if (t->readfp || t->writefp || t->cachesize > 0 || t->flt > 0) {
+    fprintf(stderr, "trans_setup: ERROR: %s is not available on a limited-area handle (there are no Legendre polynomials)\n",
+            t->readfp ? "readfp" : t->writefp ? "writefp" : t->cachesize > 0 ? "cache" : "flt");
+    return TRANS_NOTIMPL;
+  }
+  if (t->nsmax < 0) {
+    fprintf(stderr, "trans_setup: ERROR: nsmax < 0\n");
+    return TRANS_ERROR;
+  }
+  if (t->ndgux < 0) t->ndgux = t->ndgl;
+  free(t->nloen); /* nloen is constant on a limited-area handle */
+  t->nloen = (int *)malloc(sizeof(int) * (size_t)t->ndgl);
+  if (!t->nloen) return TRANS_ERROR;
+  for (int j = 0; j < t->ndgl; j++) t->nloen[j] = t->nlon;
+  emi_esetup_t cfg;
+  memset(&cfg, 0, sizeof(cfg));
+  cfg.kmsmax = t->nmsmax;
+  cfg.ksmax = t->nsmax;
+  cfg.kdgl = t->ndgl;
+  cfg.kdlon = t->nlon;
+  cfg.kdgux = t->ndgux;
+  cfg.pexwn = t->pexwn;
+  cfg.peywn = t->peywn;
+  cfg.precision = 8;
+  if (emi_esetup(&cfg, &t->handle) != 0) {
+    fprintf(stderr, "trans_setup: ERROR: %s\n", emi_last_error());
+    return TRANS_ERROR;
+  }
+  fill_sizes(t);
+  return TRANS_SUCCESS;
+}
+
 int trans_setup(struct Trans_t *t) {
   int rc = trans_init();
   if (rc) return rc;
+  if (t->llam) return setup_lam(t);
   if (t->ndgl <= 0 || (!t->nloen && t->nlon <= 0)) return TRANS_MISSING_ARG;
   if (t->flt > 0) return TRANS_NOTIMPL;
   if (t->llatlon && (t->nlon <= 0 || t->readfp || t->writefp || t->cachesize > 0)) return TRANS_NOTIMPL; /* no Legendre file of lat-lon rows */
@@ -176,21 +257,50 @@ int trans_setup(struct Trans_t *t) {
     io.len = t->cachesize;
   }
   if (emi_setup_legpol(&cfg, io.io ? &io : NULL, &t->handle) != 0) return TRANS_ERROR;
-  t->myproc = t->nproc = 1;
-  emi_inq_tasks(&t->nproc, &t->myproc);
-  emi_inq_int(t->handle, "nspec2", &t->nspec2);
-  t->nspec = t->nspec2 / 2;
-  emi_inq_int(t->handle, "nspec2g", &t->nspec2g);
-  emi_inq_int(t->handle, "nspec2mx", &t->nspec2mx);
-  emi_inq_int(t->handle, "nump", &t->nump);
-  emi_inq_int(t->handle, "ngptot", &t->ngptot);
-  emi_inq_int(t->handle, "ngptotg", &t->ngptotg);
-  emi_inq_int(t->handle, "ngptotmx", &t->ngptotmx);
+  fill_sizes(t);
   if (t->llatlon == 1) t->ngptotg -= t->nlon; /* the user's global field has nlat rows: the equator once (transi_module.F90:1140) */
   return TRANS_SUCCESS;
 }
 
+/* a limited-area handle: nmyms, and n / m of every local coefficient (four reals per (m, n), x-wavenumbers in MYMS order) */
+static int inq_one_lam(struct Trans_t *t, const char *v) {
+  static const char *gauss[] = {"rmu", "rgw", "ndglu", "nnmeng", "nmeng", "nasm0"};
+  for (size_t i = 0; i < sizeof(gauss) / sizeof(gauss[0]); i++)
+    if (!strcmp(v, gauss[i])) {
+      fprintf(stderr, "trans_inquire: ERROR: %s is a quantity of the Gaussian grid: not available on a limited-area handle\n", v);
+      return TRANS_NOTIMPL;
+    }
+  if (!strcmp(v, "nloen")) return TRANS_SUCCESS; /* filled by trans_setup */
+  if (strcmp(v, "nmyms") && strcmp(v, "nvalue") && strcmp(v, "mvalue")) return TRANS_UNRECOGNIZED_ARG;
+  if (!t->nmyms) {
+    t->nmyms = (int *)malloc(sizeof(int) * (size_t)(t->nump > 0 ? t->nump : 1));
+    if (!t->nmyms) return TRANS_ERROR;
+    if (emi_inq_int_array(t->handle, "myms", t->nmyms, t->nump)) return TRANS_ERROR;
+  }
+  if (!strcmp(v, "nmyms")) return TRANS_SUCCESS;
+  int *kntmp = (int *)malloc(sizeof(int) * (size_t)(t->nmsmax + 1));
+  int **dst = !strcmp(v, "nvalue") ? &t->nvalue : &t->mvalue;
+  if (!*dst) *dst = (int *)malloc(sizeof(int) * (size_t)(t->nspec2 > 0 ? t->nspec2 : 1));
+  if (!kntmp || !*dst || emi_inq_int_array(t->handle, "kntmp", kntmp, t->nmsmax + 1)) {
+    free(kntmp);
+    return TRANS_ERROR;
+  }
+  int k = 0;
+  for (int jm = 0; jm < t->nump; jm++) {
+    const int m = t->nmyms[jm];
+    for (int n = 0; n <= kntmp[m] && k + 4 <= t->nspec2; n++)
+      for (int j = 0; j < 4; j++) (*dst)[k++] = dst == &t->nvalue ? n : m;
+  }
+  free(kntmp);
+  return k == t->nspec2 ? TRANS_SUCCESS : TRANS_ERROR;
+}
+
 static int inq_one(struct Trans_t *t, const char *v) {
+  if (t->llam) return inq_one_lam(t, v);
+  if (!strcmp(v, "mvalue")) {
+    fprintf(stderr, "trans_inquire: ERROR: mvalue is a quantity of a limited-area handle\n");
+    return TRANS_NOTIMPL;
+  }
   const int ns = t->nsmax + 1;
   if (!strcmp(v, "rmu") || !strcmp(v, "rgw")) {
     double **dst = !strcmp(v, "rmu") ? &t->rmu : &t->rgw;
@@ -211,14 +321,21 @@ static int inq_one(struct Trans_t *t, const char *v) {
       return emi_inq_int_array(t->handle, ints[i].emi, *ints[i].dst, ints[i].len) ? TRANS_ERROR : TRANS_SUCCESS;
     }
   if (!strcmp(v, "nvalue")) {
-    if (!t->nvalue) t->nvalue = (int *)malloc(sizeof(int) * (size_t)t->nspec2);
+    /* [nspec2]: the zonal wavenumbers of THIS task, in MYMS order (with several tasks nspec2 < nspec2g) */
+    int *ms = (int *)malloc(sizeof(int) * (size_t)ns);
+    if (!t->nvalue) t->nvalue = (int *)malloc(sizeof(int) * (size_t)(t->nspec2 > 0 ? t->nspec2 : 1));
+    if (!ms || !t->nvalue || emi_inq_int_array(t->handle, "myms", ms, ns)) {
+      free(ms);
+      return TRANS_ERROR;
+    }
     int k = 0;
-    for (int m = 0; m <= t->nsmax; m++)
-      for (int n = m; n <= t->nsmax; n++) {
+    for (int jm = 0; jm < t->nump; jm++)
+      for (int n = ms[jm]; n <= t->nsmax && k + 2 <= t->nspec2; n++) {
         t->nvalue[k++] = n;
         t->nvalue[k++] = n;
       }
-    return TRANS_SUCCESS;
+    free(ms);
+    return k == t->nspec2 ? TRANS_SUCCESS : TRANS_ERROR;
   }
   if (!strcmp(v, "nloen")) return TRANS_SUCCESS; /* input, already there */
   return TRANS_UNRECOGNIZED_ARG;
@@ -259,6 +376,17 @@ static int lonlat_refused(const struct Trans_t *t, const char *who) {
   return 1;
 }
 
+/* rmeanu / rmeanv: [nvordiv] doubles of a limited-area handle, both required with wind fields (transi_module.F90:1694-1697); a
+ * Gaussian handle has none */
+static int check_means(const struct Trans_t *t, const char *who, int nvordiv, const double *rmeanu, const double *rmeanv) {
+  if (!t->llam) return (rmeanu || rmeanv) ? TRANS_NOTIMPL : TRANS_SUCCESS; /* LAM only */
+  if (nvordiv > 0 && (!rmeanu || !rmeanv)) {
+    fprintf(stderr, "%s: ERROR: Array %s was not allocated\n", who, !rmeanu ? "RMEANU" : "RMEANV");
+    return TRANS_MISSING_ARG;
+  }
+  return TRANS_SUCCESS;
+}
+
 struct DirTrans_t new_dirtrans(struct Trans_t *t) {
   struct DirTrans_t d;
   memset(&d, 0, sizeof(d));
@@ -271,7 +399,8 @@ int trans_dirtrans(struct DirTrans_t *d) {
   if (!d->trans || !d->rgp) return TRANS_MISSING_ARG;
   if (d->nscalar > 0 && !d->rspscalar) return TRANS_MISSING_ARG;
   if (d->nvordiv > 0 && (!d->rspvor || !d->rspdiv)) return TRANS_MISSING_ARG;
-  if (d->rmeanu || d->rmeanv) return TRANS_NOTIMPL; /* LAM only */
+  const int rcm = check_means(d->trans, "trans_dirtrans", d->nvordiv, d->rmeanu, d->rmeanv);
+  if (rcm) return rcm;
   if (lonlat_refused(d->trans, "trans_dirtrans")) return TRANS_NOTIMPL;
   emi_dirtrans_t a;
   memset(&a, 0, sizeof(a));
@@ -291,6 +420,8 @@ int trans_dirtrans(struct DirTrans_t *d) {
   a.kproma = (d->nproma > 0 && !d->lglobal) ? d->nproma : d->trans->ngptot;
   a.gp = d->rgp;
   a.gp_nfld = 2 * d->nvordiv + d->nscalar;
+  if (d->trans->llam) /* the means are outputs here (the struct declares them const, as the reference's does) */
+    return run_and_wait(emi_edir_trans(d->trans->handle, &a, (void *)d->rmeanu, (void *)d->rmeanv), d->trans->handle);
   return run_and_wait(emi_dir_trans(d->trans->handle, &a), d->trans->handle);
 }
 
@@ -340,7 +471,8 @@ int trans_invtrans(struct InvTrans_t *v) {
   if (!v->trans || !v->rgp) return TRANS_MISSING_ARG;
   if (v->nscalar > 0 && !v->rspscalar) return TRANS_MISSING_ARG;
   if (v->nvordiv > 0 && (!v->rspvor || !v->rspdiv)) return TRANS_MISSING_ARG;
-  if (v->rmeanu || v->rmeanv) return TRANS_NOTIMPL; /* LAM only */
+  const int rcm = check_means(v->trans, "trans_invtrans", v->nvordiv, v->rmeanu, v->rmeanv);
+  if (rcm) return rcm;
   emi_invtrans_t a;
   memset(&a, 0, sizeof(a));
   a.mem_space = EMI_MEM_AUTO; /* rgp / rsp* in device memory are used in place, host arrays are staged (emi_ptr_space) */
@@ -363,6 +495,7 @@ int trans_invtrans(struct InvTrans_t *v) {
               (v->luvder_EW ? 2 * v->nvordiv : 0);
   a.ldlatlon = v->trans->llatlon != 0;
   if (v->trans->llatlon == 1 && v->lglobal) return invtrans_lonlat_global(v, &a);
+  if (v->trans->llam) return run_and_wait(emi_einv_trans(v->trans->handle, &a, v->rmeanu, v->rmeanv), v->trans->handle);
   return run_and_wait(emi_inv_trans(v->trans->handle, &a), v->trans->handle);
 }
 
@@ -378,7 +511,8 @@ int trans_dirtrans_adj(struct DirTransAdj_t *d) {
   if (!d->trans || !d->rgp) return TRANS_MISSING_ARG;
   if (d->nscalar > 0 && !d->rspscalar) return TRANS_MISSING_ARG;
   if (d->nvordiv > 0 && (!d->rspvor || !d->rspdiv)) return TRANS_MISSING_ARG;
-  if (d->rmeanu || d->rmeanv) return TRANS_NOTIMPL;
+  const int rcm = check_means(d->trans, "trans_dirtrans_adj", d->nvordiv, d->rmeanu, d->rmeanv);
+  if (rcm) return rcm;
   if (lonlat_refused(d->trans, "trans_dirtrans_adj")) return TRANS_NOTIMPL;
   emi_dirtrans_t a;
   memset(&a, 0, sizeof(a));
@@ -389,6 +523,7 @@ int trans_dirtrans_adj(struct DirTransAdj_t *d) {
   a.kproma = (d->nproma > 0 && !d->lglobal) ? d->nproma : d->trans->ngptot;
   a.gp = d->rgp; /* written */
   a.gp_nfld = 2 * d->nvordiv + d->nscalar;
+  if (d->trans->llam) return run_and_wait(emi_edir_transad(d->trans->handle, &a, d->rmeanu, d->rmeanv), d->trans->handle);
   return run_and_wait(emi_dir_transad(d->trans->handle, &a), d->trans->handle);
 }
 struct InvTransAdj_t new_invtrans_adj(struct Trans_t *t) {
@@ -402,7 +537,8 @@ int trans_invtrans_adj(struct InvTransAdj_t *v) {
   if (!v->trans || !v->rgp) return TRANS_MISSING_ARG;
   if (v->nscalar > 0 && !v->rspscalar) return TRANS_MISSING_ARG;
   if (v->nvordiv > 0 && (!v->rspvor || !v->rspdiv)) return TRANS_MISSING_ARG;
-  if (v->rmeanu || v->rmeanv) return TRANS_NOTIMPL;
+  const int rcm = check_means(v->trans, "trans_invtrans_adj", v->nvordiv, v->rmeanu, v->rmeanv);
+  if (rcm) return rcm;
   if (lonlat_refused(v->trans, "trans_invtrans_adj")) return TRANS_NOTIMPL;
   if (check_global(v->trans, v->lglobal)) return TRANS_ERROR;
   emi_invtrans_t a;
@@ -417,6 +553,8 @@ int trans_invtrans_adj(struct InvTransAdj_t *v) {
   a.gp = v->rgp;
   a.gp_nfld = 2 * v->nvordiv + v->nscalar + (v->lscalarders ? 2 * v->nscalar : 0) + (v->lvordivgp ? 2 * v->nvordiv : 0) +
               (v->luvder_EW ? 2 * v->nvordiv : 0);
+  if (v->trans->llam) /* the means are outputs here */
+    return run_and_wait(emi_einv_transad(v->trans->handle, &a, (void *)v->rmeanu, (void *)v->rmeanv), v->trans->handle);
   return run_and_wait(emi_inv_transad(v->trans->handle, &a), v->trans->handle);
 }
 
@@ -455,7 +593,7 @@ int trans_distgrid(struct DistGrid_t *a) {
   if (!a->trans || !a->rgp || !a->nfrom || a->nfld <= 0 || a->nproma <= 0) return TRANS_MISSING_ARG;
   const long ng = a->trans->ngptot, np = a->nproma, nb = (ng - 1) / np + 1;
   if (a->ngpblks < nb) return TRANS_ERROR;
-  if (emi_dist_grid(a->trans->handle, a->rgpg, a->nfld, a->nfrom, NULL, a->nproma, a->rgp)) return TRANS_ERROR;
+  if ((a->trans->llam ? emi_edist_grid : emi_dist_grid)(a->trans->handle, a->rgpg, a->nfld, a->nfrom, NULL, a->nproma, a->rgp)) return TRANS_ERROR;
   /* the padding of the last NPROMA block (and any further block): zero, as the Fortran DIST_GRID of the shim leaves it -- a
    * malloc'ed rgp must not carry NaNs into a later trans_dirtrans or a checksum */
   for (long b = nb - 1; b < a->ngpblks; b++) {
@@ -467,7 +605,7 @@ int trans_distgrid(struct DistGrid_t *a) {
 int trans_gathgrid(struct GathGrid_t *a) {
   if (a->count++ > 0) return TRANS_STALE_ARG;
   if (!a->trans || !a->rgp || !a->nto || a->nfld <= 0 || a->nproma <= 0) return TRANS_MISSING_ARG;
-  return emi_gath_grid(a->trans->handle, a->rgpg, a->nfld, a->nto, a->nproma, a->rgp) ? TRANS_ERROR : TRANS_SUCCESS;
+  return (a->trans->llam ? emi_egath_grid : emi_gath_grid)(a->trans->handle, a->rgpg, a->nfld, a->nto, a->nproma, a->rgp) ? TRANS_ERROR : TRANS_SUCCESS;
 }
 /* rspecg is [nspec2g][nfldg] here (Fortran PSPECG(nfldg, nspec2g), transi.h:1140-1186), [nfldg][nspec2g] in the C-ABI */
 static int count_mine(const struct Trans_t *t, const int *task, int nfld) {
@@ -488,7 +626,7 @@ int trans_distspec(struct DistSpec_t *a) {
     for (size_t i = 0; i < ng; i++)
       for (int f = 0; f < nm; f++) tmp[(size_t)f * ng + i] = a->rspecg[i * (size_t)nm + f];
   }
-  const int rc = emi_dist_spec(a->trans->handle, tmp, a->nfld, a->nfrom, NULL, a->rspec);
+  const int rc = (a->trans->llam ? emi_edist_spec : emi_dist_spec)(a->trans->handle, tmp, a->nfld, a->nfrom, NULL, a->rspec);
   free(tmp);
   return rc ? TRANS_ERROR : TRANS_SUCCESS;
 }
@@ -503,7 +641,7 @@ int trans_gathspec(struct GathSpec_t *a) {
     tmp = (double *)malloc(sizeof(double) * ng * (size_t)nm);
     if (!tmp) return TRANS_ERROR;
   }
-  const int rc = emi_gath_spec(a->trans->handle, tmp, a->nfld, a->nto, a->rspec);
+  const int rc = (a->trans->llam ? emi_egath_spec : emi_gath_spec)(a->trans->handle, tmp, a->nfld, a->nto, a->rspec);
   if (!rc)
     for (size_t i = 0; i < ng; i++)
       for (int f = 0; f < nm; f++) a->rspecg[i * (size_t)nm + f] = tmp[(size_t)f * ng + i];
@@ -522,8 +660,13 @@ struct SpecNorm_t new_specnorm(struct Trans_t *t) {
 int trans_specnorm(struct SpecNorm_t *s) {
   if (s->count++ > 0) return TRANS_STALE_ARG;
   if (!s->trans || !s->rspec || !s->rnorm || s->nfld <= 0) return TRANS_MISSING_ARG;
-  if (s->rmet) return TRANS_NOTIMPL;
-  return emi_specnorm(s->trans->handle, EMI_MEM_AUTO, s->rspec, s->nfld, s->rnorm) ? TRANS_ERROR : TRANS_SUCCESS;
+  const struct Trans_t *t = s->trans;
+  if (t->llam) /* rmet: ESPECNORM's zero-based metric of nspec2g / 4 + 1 elements (transi_mi.h) */
+    return emi_especnorm(t->handle, EMI_MEM_AUTO, s->rspec, s->nfld, s->rmet, s->rmet ? t->nspec2g / 4 + 1 : 0, s->rnorm) ? TRANS_ERROR : TRANS_SUCCESS;
+  if (s->rmet && t->llatlon) return TRANS_NOTIMPL;
+  if (s->rmet) /* SPECNORM's PMET(0:NSMAX) */
+    return emi_specnorm_met(t->handle, EMI_MEM_AUTO, s->rspec, s->nfld, s->rmet, t->nsmax + 1, NULL, 0, s->rnorm) ? TRANS_ERROR : TRANS_SUCCESS;
+  return emi_specnorm(t->handle, EMI_MEM_AUTO, s->rspec, s->nfld, s->rnorm) ? TRANS_ERROR : TRANS_SUCCESS;
 }
 
 struct VorDivToUV_t new_vordiv_to_UV(void) {
@@ -547,7 +690,7 @@ int trans_delete(struct Trans_t *t) {
   int rc = TRANS_SUCCESS;
   if (t->handle) rc = emi_release(t->handle) ? TRANS_ERROR : TRANS_SUCCESS;
   free(t->readfp), free(t->writefp);
-  free(t->nloen), free(t->nmyms), free(t->nasm0), free(t->nvalue), free(t->ndglu), free(t->nnmeng), free(t->rmu), free(t->rgw);
+  free(t->nloen), free(t->nmyms), free(t->nasm0), free(t->nvalue), free(t->ndglu), free(t->nnmeng), free(t->rmu), free(t->rgw), free(t->mvalue);
   memset(t, 0, sizeof(*t));
   return rc;
 }

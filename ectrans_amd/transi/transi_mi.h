@@ -6,8 +6,22 @@
  * (rgp[ngpblks][nfld][nproma], rsp[nspec2][nfld], transi.h:908-921), same return convention
  * (TRANS_SUCCESS = 0, negative error codes, trans_error_msg()).
  *
- * Not provided (outside SURVEY.md section 8): LAM, rmeanu/rmeanv (lglobal is honoured: one task, global == local).
- * They return TRANS_NOTIMPL instead of being silently ignored.
+ * What a handle does not serve returns TRANS_NOTIMPL instead of being silently ignored (lglobal is honoured: one task,
+ * global == local).
+ *
+ * Limited-area (LAM) handles (trans_set_resol_lam, trans_set_trunc_lam; transi.h:838-898): a plane grid of ny rows of nx points,
+ * bi-Fourier transforms, the spectrum truncated to the ellipse of (trunc_x, trunc_y).  trans_setup goes to ESETUP_TRANS; every
+ * routine below dispatches on Trans_t.llam to the E-routine of the C-ABI (EINV_TRANS, EDIR_TRANS, their adjoints, EDIST_x, EGATH_x,
+ * ESPECNORM).  rmeanu / rmeanv are [nvordiv] doubles in HOST or device memory, both required with nvordiv > 0: outputs of
+ * trans_dirtrans and trans_invtrans_adj, inputs of trans_invtrans and trans_dirtrans_adj; on a Gaussian handle they must stay NULL.
+ * Not served on a LAM handle, each with a message on stderr: readfp / writefp / cache / flt > 0 at trans_setup, and the Gaussian
+ * quantities rmu, rgw, ndglu, nnmeng, nasm0 of trans_inquire.  The spectral layout is ESETUP_TRANS's: per x-wavenumber m and
+ * n = 0 .. KNTMP(m) four reals; trans_inquire("nvalue,mvalue") gives n and m of every local coefficient.
+ *
+ * SpecNorm_t.rmet: on a Gaussian handle nsmax + 1 doubles, rmet[n] the weight of total wavenumber n (SPECNORM's PMET).  On a LAM
+ * handle ESPECNORM's convention: zero-based, nspec2g / 4 + 1 doubles, (m, n) reads rmet[NPME(m) + n] and element 0 is never read --
+ * the reference's transi maps rmet to a pointer of nsmax + 1 elements there, which is too short for what ESPECNORM reads.  On a
+ * lat-lon handle rmet returns TRANS_NOTIMPL.
  *
  * Regular lat-lon grids (trans_set_resol_lonlat, transi.h:186): trans_invtrans only.  The series is evaluated exactly on the
  * grid's rows (the reference interpolates from a Gaussian grid, and its GPU build refuses lonlat).  nlat odd: poles and
@@ -61,6 +75,12 @@ struct Trans_t {
   int *nnmeng;  /* [ndgl] NMEN per latitude */
   double *rmu;  /* [ndgl] sin(latitude) */
   double *rgw;  /* [ndgl] Gaussian weights (sum = 1) */
+  /* limited-area handles (transi.h:838-845; trans_set_resol_lam, trans_set_trunc_lam) */
+  int llam;            /* 0: the sphere; 1: a limited-area handle */
+  int nmsmax;          /* truncation in x (nsmax: in y) */
+  int ndgux;           /* last row outside the extension zone; < 0: ndgl */
+  double pexwn, peywn; /* wavenumber units 2 pi / (nx dx), 2 pi / (ny dy) */
+  int *mvalue;         /* [nspec2] m of every coefficient, on demand by trans_inquire (LAM handles only) */
 };
 
 struct DirTrans_t {
@@ -68,7 +88,7 @@ struct DirTrans_t {
   double *rspscalar;  /* [nspec2][nscalar] */
   double *rspvor;     /* [nspec2][nvordiv] */
   double *rspdiv;     /* [nspec2][nvordiv] */
-  const double *rmeanu, *rmeanv; /* LAM only: must stay NULL */
+  const double *rmeanu, *rmeanv; /* LAM only, [nvordiv], WRITTEN (const as in the reference); a Gaussian handle: must stay NULL */
   int nproma, nscalar, nvordiv, ngpblks, lglobal;
   struct Trans_t *trans;
   int count; /* a DirTrans_t is single use, as in the reference (transi_module.F90:1661-1666) */
@@ -115,7 +135,7 @@ int trans_invtrans_adj(struct InvTransAdj_t *);
 struct SpecNorm_t {
   const double *rspec; /* [nspec2][nfld] */
   int nmaster;
-  const double *rmet; /* must stay NULL */
+  const double *rmet; /* NULL, or the metric: [nsmax + 1] on a Gaussian handle, [nspec2g / 4 + 1] on a LAM handle (see above) */
   double *rnorm;      /* [nfld] */
   int nfld;
   struct Trans_t *trans;
@@ -134,6 +154,8 @@ int trans_new(struct Trans_t *);
 int trans_set_resol(struct Trans_t *, int ndgl, const int *nloen);
 int trans_set_resol_lonlat(struct Trans_t *, int nlon, int nlat);   /* transi.h:186 */
 int trans_set_trunc(struct Trans_t *, int nsmax);
+int trans_set_resol_lam(struct Trans_t *, int nx, int ny, double dx, double dy); /* transi.h:883 */
+int trans_set_trunc_lam(struct Trans_t *, int trunc_x, int trunc_y);             /* transi.h:898 */
 int trans_set_read(struct Trans_t *, const char *filepath);          /* transi.h:192 */
 int trans_set_write(struct Trans_t *, const char *filepath);         /* transi.h:193 */
 int trans_set_cache(struct Trans_t *, const void *cache, size_t cachesize); /* transi.h:194 */

@@ -306,6 +306,23 @@ int emi_specnorm(int kresol, int mem_space, const void *spec, int nfld, double *
 /* SPECNORM with KVSET (NPRTRV > 1): spec holds the nfld fields of this task's V-set, norms_g (host) receives the norms of all
  * nfld_g fields, kvset[f] = V-set of global field f.  Collective over all tasks (host collectives).                   */
 int emi_specnorm_kvset(int kresol, int mem_space, const void *spec, int nfld, const int *kvset, int nfld_g, double *norms_g);
+/* SPECNORM with PMET (specnorm.h:12, spnormd_mod.F90:36-53): the metric PMET(0:NSMAX) weights the coefficients of total wavenumber n,
+ *   PNORM(f)^2 = sum over m = 0 .. NSMAX of c_m sum over n = m .. NSMAX of pmet[n] (re^2 + im^2),  c_0 = 1 (real parts only), c_m = 2.
+ * pmet: npmet >= NSMAX + 1 reals of the handle's precision in HOST memory, read from element 0.  spec: host or device memory; the call
+ * runs on the null stream behind the last transform of the resolution.  Sums are in double in both precisions, and the summation
+ * order of one (m, f) depends on NSMAX - m alone: the norms are the same bytes for any number of fields in the call, any position of
+ * the field and any number of tasks.  A kernel of its own (k_specnorm_met): emi_specnorm keeps its kernel and its bits.
+ * emi_specnorm_met_partial: sums (host) = double[nump][nfld], the c_m-weighted sum of this task's wavenumbers in MYMS order.
+ * emi_specnorm_met: norms (host) on every task; several tasks gather the sums through the host collectives.  kvset == NULL: the norms of
+ * the nfld fields of spec (nfld_g is ignored); kvset != NULL: as emi_specnorm_kvset, norms holds nfld_g elements.
+ * A handle set up with LDLL is refused (EMI_ERR_UNSUPPORTED), although emi_specnorm itself serves one: the metric is defined for the
+ * Gaussian handles, and a handle that serves INV_TRANS with LDLATLON only has no caller for it.
+ * emi_specnorm_last_ms: with emi_set_profile(1), the device time (ms) of the kernel alone of the last emi_specnorm* call
+ * (k_specnorm or k_specnorm_met), between two events on the null stream.                                                          */
+int emi_specnorm_last_ms(double *ms);
+int emi_specnorm_met_partial(int kresol, int mem_space, const void *spec, int nfld, const void *pmet, int npmet, double *sums);
+int emi_specnorm_met(int kresol, int mem_space, const void *spec, int nfld, const void *pmet, int npmet, const int *kvset, int nfld_g,
+                     double *norms);
 /* NPRTRW, NPRTRV, MYSETW, MYSETV (sump_trans0_mod.F90:49, pe2set_mod.F90:111-112) of the initialised library                */
 int emi_inq_vsets(int *nprtrw, int *nprtrv, int *mysetw, int *mysetv);
 
