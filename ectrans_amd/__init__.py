@@ -153,6 +153,12 @@ def _bind(L):
     L.emi_dist_grid.argtypes = [C.c_int, C.c_void_p, C.c_int, ip, ip, C.c_int, C.c_void_p]
     L.emi_gath_grid.argtypes = [C.c_int, C.c_void_p, C.c_int, ip, C.c_int, C.c_void_p]
     L.emi_inq_tasks.argtypes = [ip, ip]
+    if hasattr(L, "emi_dist_spec_m"):  # (an older build loaded for an A/B run)
+        for e in ("", "e"):
+            getattr(L, "emi_%sdist_spec_m" % e).argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, ip, ip, C.c_int, C.c_void_p]
+            getattr(L, "emi_%sgath_spec_m" % e).argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, ip, C.c_int, C.c_void_p]
+            getattr(L, "emi_%sdist_grid_m" % e).argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, ip, ip, C.c_int, C.c_int, C.c_void_p]
+            getattr(L, "emi_%sgath_grid_m" % e).argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, ip, C.c_int, C.c_int, C.c_void_p]
     L.emi_inq_init.argtypes = [ip, dp]
     L.emi_set_nprtrv.argtypes = [C.c_int]
     if hasattr(L, "emi_esetup"):  # (an older build loaded for an A/B run)
@@ -182,10 +188,14 @@ def _bind(L):
     return L
 
 
+_EMULATOR = [False]  # set by _use_library_for_tests alone
+
+
 def lib():
     """The HIP shared library.  No fallback: a missing library is an error."""
     global _L
     if _L is None:
+        _EMULATOR[0] = False
         if not os.path.exists(_LIBPATH):
             raise TransError("libectrans_mi.so is not built (run __graft_entry__.build()); "
                              "ectrans_amd has no CPU implementation")
@@ -197,6 +207,7 @@ def _use_library_for_tests(path):
     """tests/emu only: point the wrapper at the CPU functional emulator build."""
     global _L
     _L = _bind(C.CDLL(path))
+    _EMULATOR[0] = True
     return _L
 
 
@@ -964,20 +975,93 @@ def _iptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_int))
 
 
-def dist_spec(kresol, pspecg, kfdistg, kfrom=1):
+def _on_emulator():
+    """tests/emu only: the CPU functional emulator is loaded (_use_library_for_tests), whose "device" memory is host memory (numpy
+    arrays in place)"""
+    return _EMULATOR[0]
+
+
+def _gs_device_of(like):
+    import torch
+    if _is_torch(like) and like.is_cuda:
+        return like.device
+    return torch.device(_DIST["device"] if _DIST["device"] and str(_DIST["device"]).startswith("cuda") else "cuda")
+
+
+def _gs_zeros(shape, dt, on_device, like=None):
+    """a zero array for a result of the _m routines: a device tensor, or numpy (host memory; the emulator's device memory too)"""
+    if not on_device or _on_emulator():
+        return np.zeros(shape, dtype=dt)
+    import torch
+    return torch.zeros(shape, dtype=getattr(torch, np.dtype(dt).name), device=_gs_device_of(like))
+
+
+def _gs_move(a, dt, on_device, like=None):
+    """array `a` (numpy or torch, any memory) as a C-contiguous array of dtype dt in the wanted memory"""
+    if not on_device or _on_emulator():
+        return np.ascontiguousarray(_np(a), dtype=dt)
+    import torch
+    t = a if _is_torch(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=dt))
+    return t.to(device=_gs_device_of(like if like is not None else a), dtype=getattr(torch, np.dtype(dt).name)).contiguous()
+
+
+def _gs_ptr(a, dt, who, name):
+    """pointer of an array of the _m routines used in place: a contiguous numpy array or torch tensor of the handle's precision"""
+    if a is None:
+        return None
+    if _is_torch(a):
+        if not a.is_contiguous() or str(a.dtype) != "torch." + np.dtype(dt).name:
+            raise TransError("%s: %s must be a contiguous %s tensor" % (who, name, np.dtype(dt).name))
+        return a.data_ptr()
+    if not (isinstance(a, np.ndarray) and a.dtype == np.dtype(dt) and a.flags.c_contiguous):
+        raise TransError("%s: %s must be a C-contiguous %s array" % (who, name, np.dtype(dt).name))
+    return a.ctypes.data
+
+
+def _gs_spaces(who, mem_space, glob_space, glob=None):
+    """(loc_space, glob_space) of a call with mem_space= or glob_space=; glob: the global array where the caller passes one"""
+    ls = EMI_MEM_AUTO if mem_space is None else int(mem_space)
+    if glob_space is None:
+        gs = EMI_MEM_DEVICE if (_is_torch(glob) and glob.is_cuda) else EMI_MEM_HOST
+    else:
+        gs = int(glob_space)
+    if gs == EMI_MEM_AUTO:
+        gs = EMI_MEM_DEVICE if (_is_torch(glob) and glob.is_cuda) else EMI_MEM_HOST
+    if ls not in (EMI_MEM_HOST, EMI_MEM_DEVICE, EMI_MEM_AUTO) or gs not in (EMI_MEM_HOST, EMI_MEM_DEVICE):
+        raise TransError("%s: mem_space / glob_space must be EMI_MEM_HOST, EMI_MEM_DEVICE or EMI_MEM_AUTO" % who)
+    return ls, gs
+
+
+def dist_spec(kresol, pspecg, kfdistg, kfrom=1, mem_space=None, glob_space=None):
     """DIST_SPEC (dist_spec.h:11) over emi_dist_spec: global spectral fields `pspecg` (nspec2g, kfdistg), field f held
     by task kfrom[f] (1-based; the columns of other tasks' fields are not read, the array may be None on a task that is
-    the source of none), -> this task's (nspec2, kfdistg) local array."""
-    return _dist_spec("", kresol, pspecg, kfdistg, kfrom, None)
+    the source of none), -> this task's (nspec2, kfdistg) local array.
+    mem_space=EMI_MEM_DEVICE (emi_dist_spec_m): the local array is laid out on the device and returned as a device tensor (a numpy
+    array on the CPU emulator of the tests); glob_space: the memory the global image is consumed from (default: where `pspecg` lives).
+    The local array is created by the call, so there is nothing for EMI_MEM_AUTO to classify: mem_space=EMI_MEM_AUTO, and glob_space=
+    given alone, mean EMI_MEM_DEVICE; only mem_space=EMI_MEM_HOST gives a numpy result through the host path."""
+    return _dist_spec("", kresol, pspecg, kfdistg, kfrom, None, mem_space, glob_space)
 
 
-def _dist_spec(_e, kresol, pspecg, kfdistg, kfrom, ksort):
+def _dist_spec(_e, kresol, pspecg, kfdistg, kfrom, ksort, mem_space=None, glob_space=None):
     """dist_spec (_e = "") / edist_spec (_e = "e")"""
     dt = real_dtype(kresol)
     ns2g, ns2, me = trans_inq(kresol, "nspec2g"), trans_inq(kresol, "nspec2"), trans_inq(kresol, "myproc")
     who = _e.upper() + "DIST_SPEC"
     kfrom = _roots(kfrom, kfdistg, who + ":KFROM")
     mine = np.flatnonzero(kfrom == me)
+    ks = None if ksort is None else np.ascontiguousarray(ksort, dtype=np.int32)
+    if mem_space is not None or glob_space is not None:
+        ls, gs = _gs_spaces(who, mem_space, glob_space, pspecg)
+        g = None
+        if mine.size:
+            if pspecg.shape[0] != ns2g:
+                raise TransError("%s: PSPECG must have shape (nspec2g=%d, nfld)" % (who, ns2g))
+            g = _gs_move(pspecg[:, mine.tolist()].T, dt, gs == EMI_MEM_DEVICE)  # [n_mine][nspec2g]
+        out = _gs_zeros((ns2, kfdistg), dt, ls != EMI_MEM_HOST, pspecg)
+        _chk(getattr(lib(), "emi_%sdist_spec_m" % _e)(kresol, gs, _gs_ptr(g, dt, who, "PSPECG"), kfdistg, _iptr(kfrom), None if ks is None else _iptr(ks),
+                                                      EMI_MEM_HOST if ls == EMI_MEM_HOST else EMI_MEM_DEVICE, _gs_ptr(out, dt, who, "PSPEC")))
+        return out
     g = None
     if mine.size:
         a = _np(pspecg)
@@ -985,103 +1069,138 @@ def _dist_spec(_e, kresol, pspecg, kfdistg, kfrom, ksort):
             raise TransError("%s: PSPECG must have shape (nspec2g=%d, nfld)" % (who, ns2g))
         g = np.ascontiguousarray(a[:, mine].T, dtype=dt)  # [n_mine][nspec2g]
     out = np.zeros((ns2, kfdistg), dtype=dt)
-    ks = None if ksort is None else np.ascontiguousarray(ksort, dtype=np.int32)
     _chk(getattr(lib(), "emi_%sdist_spec" % _e)(kresol, None if g is None else g.ctypes.data, kfdistg, _iptr(kfrom),
                                                 None if ks is None else _iptr(ks), out.ctypes.data))
     return out
 
 
-def gath_spec(kresol, pspec, kfgathg, kto=1):
+def gath_spec(kresol, pspec, kfgathg, kto=1, mem_space=None, glob_space=None):
     """GATH_SPEC (gath_spec.h:11) over emi_gath_spec: local (nspec2, kfgathg) -> global (nspec2g, n_mine) holding the
-    fields this task is the target of (None if it is the target of none)."""
-    return _gath_spec("", kresol, pspec, kfgathg, kto)
+    fields this task is the target of (None if it is the target of none).
+    mem_space=EMI_MEM_DEVICE (emi_gath_spec_m): `pspec` is a contiguous device tensor used in place (a numpy array on the CPU emulator
+    of the tests); glob_space: the memory of the returned global image (default host: a numpy array; EMI_MEM_DEVICE: a device
+    tensor, the (nspec2g, n_mine) view of the [n_mine][nspec2g] image)."""
+    return _gath_spec("", kresol, pspec, kfgathg, kto, mem_space, glob_space)
 
 
-def _gath_spec(_e, kresol, pspec, kfgathg, kto):
+def _gath_spec(_e, kresol, pspec, kfgathg, kto, mem_space=None, glob_space=None):
     """gath_spec (_e = "") / egath_spec (_e = "e")"""
     dt = real_dtype(kresol)
     ns2g, me = trans_inq(kresol, "nspec2g"), trans_inq(kresol, "myproc")
-    kto = _roots(kto, kfgathg, _e.upper() + "GATH_SPEC:KTO")
-    loc = np.ascontiguousarray(_np(pspec), dtype=dt)
+    who = _e.upper() + "GATH_SPEC"
+    kto = _roots(kto, kfgathg, who + ":KTO")
     nm = int((kto == me).sum())
+    if mem_space is not None or glob_space is not None:
+        ls, gs = _gs_spaces(who, mem_space, glob_space)
+        if pspec.ndim != 2 or pspec.shape[1] != kfgathg or pspec.shape[0] != trans_inq(kresol, "nspec2"):
+            raise TransError("%s: PSPEC must have shape (nspec2, kfgathg=%d)" % (who, kfgathg))
+        g = _gs_zeros((nm, ns2g), dt, gs == EMI_MEM_DEVICE, pspec) if nm else None
+        _chk(getattr(lib(), "emi_%sgath_spec_m" % _e)(kresol, gs, _gs_ptr(g, dt, who, "PSPECG"), kfgathg, _iptr(kto), ls, _gs_ptr(pspec, dt, who, "PSPEC")))
+        return None if g is None else (g.t() if _is_torch(g) else np.ascontiguousarray(g.T))
+    loc = np.ascontiguousarray(_np(pspec), dtype=dt)
     g = np.zeros((nm, ns2g), dtype=dt) if nm else None
     _chk(getattr(lib(), "emi_%sgath_spec" % _e)(kresol, None if g is None else g.ctypes.data, kfgathg, _iptr(kto), loc.ctypes.data))
     return None if g is None else np.ascontiguousarray(g.T)
 
 
-def gath_grid(kresol, pgp, kfgathg, kto=1):
+def gath_grid(kresol, pgp, kfgathg, kto=1, mem_space=None, glob_space=None):
     """GATH_GRID (gath_grid.h:11) over emi_gath_grid: local blocked grid array (ngpblks, kfgathg, nproma) -> global
-    (n_mine, ngptotg) of the fields this task is the target of (None if none)."""
-    return _gath_grid("", kresol, pgp, kfgathg, kto)
+    (n_mine, ngptotg) of the fields this task is the target of (None if none).
+    mem_space=EMI_MEM_DEVICE (emi_gath_grid_m): `pgp` is a contiguous device tensor used in place (a numpy array on the CPU emulator
+    of the tests); glob_space: the memory of the returned global image (default host)."""
+    return _gath_grid("", kresol, pgp, kfgathg, kto, mem_space, glob_space)
 
 
-def _gath_grid(_e, kresol, pgp, kfgathg, kto):
+def _gath_grid(_e, kresol, pgp, kfgathg, kto, mem_space=None, glob_space=None):
     """gath_grid (_e = "") / egath_grid (_e = "e")"""
     dt = real_dtype(kresol)
     ngg, me = trans_inq(kresol, "ngptotg"), trans_inq(kresol, "myproc")
     who = _e.upper() + "GATH_GRID"
     kto = _roots(kto, kfgathg, who + ":KTO")
+    nm = int((kto == me).sum())
+    if mem_space is not None or glob_space is not None:
+        ls, gs = _gs_spaces(who, mem_space, glob_space)
+        ngl = trans_inq(kresol, "ngptot")
+        if pgp.ndim != 3 or pgp.shape[1] != kfgathg or pgp.shape[0] != (ngl - 1) // int(pgp.shape[2]) + 1:
+            raise TransError("%s: PGP must have shape (ngpblks, kfgathg=%d, nproma)" % (who, kfgathg))
+        g = _gs_zeros((nm, ngg), dt, gs == EMI_MEM_DEVICE, pgp) if nm else None
+        _chk(getattr(lib(), "emi_%sgath_grid_m" % _e)(kresol, gs, _gs_ptr(g, dt, who, "PGPG"), kfgathg, _iptr(kto), int(pgp.shape[2]), ls,
+                                                      _gs_ptr(pgp, dt, who, "PGP")))
+        return g
     loc = np.ascontiguousarray(_np(pgp), dtype=dt)
     if loc.ndim != 3 or loc.shape[1] != kfgathg:
         raise TransError("%s: PGP must have shape (ngpblks, kfgathg=%d, nproma)" % (who, kfgathg))
-    nm = int((kto == me).sum())
     g = np.zeros((nm, ngg), dtype=dt) if nm else None
     _chk(getattr(lib(), "emi_%sgath_grid" % _e)(kresol, None if g is None else g.ctypes.data, kfgathg, _iptr(kto), loc.shape[2], loc.ctypes.data))
     return g
 
 
-def dist_grid(kresol, pgpg, kfdistg, kfrom=1, kproma=None):
+def dist_grid(kresol, pgpg, kfdistg, kfrom=1, kproma=None, mem_space=None, glob_space=None):
     """DIST_GRID (dist_grid.h:11) over emi_dist_grid: global (kfdistg, ngptotg) on task kfrom[f] -> this task's blocked
-    (ngpblks, kfdistg, nproma) array (padding of the last block zero)."""
-    return _dist_grid("", kresol, pgpg, kfdistg, kfrom, kproma, None)
+    (ngpblks, kfdistg, nproma) array (padding of the last block zero).
+    mem_space=EMI_MEM_DEVICE (emi_dist_grid_m): the local array is laid out on the device and returned as a device tensor (a numpy
+    array on the CPU emulator of the tests); glob_space: the memory the global image is consumed from (default: where `pgpg` lives).
+    mem_space=EMI_MEM_AUTO, and glob_space= given alone, mean EMI_MEM_DEVICE, as for ``dist_spec``."""
+    return _dist_grid("", kresol, pgpg, kfdistg, kfrom, kproma, None, mem_space, glob_space)
 
 
-def _dist_grid(_e, kresol, pgpg, kfdistg, kfrom, kproma, ksort):
+def _dist_grid(_e, kresol, pgpg, kfdistg, kfrom, kproma, ksort, mem_space=None, glob_space=None):
     """dist_grid (_e = "") / edist_grid (_e = "e")"""
     dt = real_dtype(kresol)
     ngl, ngg, me = trans_inq(kresol, "ngptot"), trans_inq(kresol, "ngptotg"), trans_inq(kresol, "myproc")
     who = _e.upper() + "DIST_GRID"
     kfrom = _roots(kfrom, kfdistg, who + ":KFROM")
     mine = np.flatnonzero(kfrom == me)
+    nproma = int(kproma) if kproma else ngl
+    ks = None if ksort is None else np.ascontiguousarray(ksort, dtype=np.int32)
+    if mem_space is not None or glob_space is not None:
+        ls, gs = _gs_spaces(who, mem_space, glob_space, pgpg)
+        g = None
+        if mine.size:
+            if pgpg.shape[-1] != ngg:
+                raise TransError("%s: PGPG must have shape (nfld, ngptotg=%d)" % (who, ngg))
+            g = _gs_move(pgpg[mine.tolist()], dt, gs == EMI_MEM_DEVICE)
+        out = _gs_zeros(((ngl - 1) // nproma + 1, kfdistg, nproma), dt, ls != EMI_MEM_HOST, pgpg)
+        _chk(getattr(lib(), "emi_%sdist_grid_m" % _e)(kresol, gs, _gs_ptr(g, dt, who, "PGPG"), kfdistg, _iptr(kfrom), None if ks is None else _iptr(ks),
+                                                      nproma, EMI_MEM_HOST if ls == EMI_MEM_HOST else EMI_MEM_DEVICE, _gs_ptr(out, dt, who, "PGP")))
+        return out
     g = None
     if mine.size:
         a = _np(pgpg)
         if a.shape[-1] != ngg:
             raise TransError("%s: PGPG must have shape (nfld, ngptotg=%d)" % (who, ngg))
         g = np.ascontiguousarray(a[mine], dtype=dt)
-    nproma = int(kproma) if kproma else ngl
     out = np.zeros(((ngl - 1) // nproma + 1, kfdistg, nproma), dtype=dt)
-    ks = None if ksort is None else np.ascontiguousarray(ksort, dtype=np.int32)
     _chk(getattr(lib(), "emi_%sdist_grid" % _e)(kresol, None if g is None else g.ctypes.data, kfdistg, _iptr(kfrom),
                                                 None if ks is None else _iptr(ks), nproma, out.ctypes.data))
     return out
 
 
-def edist_spec(kresol, pspecg, kfdistg, kfrom=1, ksort=None):
+def edist_spec(kresol, pspecg, kfdistg, kfrom=1, ksort=None, mem_space=None, glob_space=None):
     """EDIST_SPEC (edist_spec.h): ``dist_spec`` on a handle of ``esetup_trans``.  A global spectral field is the one-task layout:
     m = 0 .. KMSMAX ascending, 4 (KNTMP(m) + 1) reals each.  ksort: field f lands in column ksort[f] (1-based) of the result."""
-    return _dist_spec("e", kresol, pspecg, kfdistg, kfrom, ksort)
+    return _dist_spec("e", kresol, pspecg, kfdistg, kfrom, ksort, mem_space, glob_space)
 
 
-def egath_spec(kresol, pspec, kfgathg, kto=1, ksmax=None, kmsmax=None, ldza0ip=False):
+def egath_spec(kresol, pspec, kfgathg, kto=1, ksmax=None, kmsmax=None, ldza0ip=False, mem_space=None, glob_space=None):
     """EGATH_SPEC (egath_spec.h): ``gath_spec`` on a handle of ``esetup_trans``.  The whole spectrum only: ksmax / kmsmax are accepted
     where they equal the handle's, and ldza0ip, which addresses the spherical layout, is refused."""
     if (ksmax is not None and int(ksmax) != etrans_inq(kresol, "nsmax")) or (kmsmax is not None and int(kmsmax) != etrans_inq(kresol, "nmsmax")):
         raise TransError("EGATH_SPEC: KSMAX / KMSMAX (truncated gather) not supported")
     if ldza0ip:
         raise TransError("EGATH_SPEC: LDZA0IP not supported")
-    return _gath_spec("e", kresol, pspec, kfgathg, kto)
+    return _gath_spec("e", kresol, pspec, kfgathg, kto, mem_space, glob_space)
 
 
-def edist_grid(kresol, pgpg, kfdistg, kfrom=1, kproma=None, ksort=None):
+def edist_grid(kresol, pgpg, kfdistg, kfrom=1, kproma=None, ksort=None, mem_space=None, glob_space=None):
     """EDIST_GRID (edist_grid.h): ``dist_grid`` on a handle of ``esetup_trans``.  A global grid field is the NDGL x NDLON points row
     after row.  ksort: field f lands in slot ksort[f] (1-based) of the result."""
-    return _dist_grid("e", kresol, pgpg, kfdistg, kfrom, kproma, ksort)
+    return _dist_grid("e", kresol, pgpg, kfdistg, kfrom, kproma, ksort, mem_space, glob_space)
 
 
-def egath_grid(kresol, pgp, kfgathg, kto=1):
+def egath_grid(kresol, pgp, kfgathg, kto=1, mem_space=None, glob_space=None):
     """EGATH_GRID (egath_grid.h): ``gath_grid`` on a handle of ``esetup_trans``."""
-    return _gath_grid("e", kresol, pgp, kfgathg, kto)
+    return _gath_grid("e", kresol, pgp, kfgathg, kto, mem_space, glob_space)
 
 
 def trans_release(kresol):

@@ -2202,7 +2202,10 @@ struct PhaseTimer {
     }
   }
 #else
-  void begin(bool, bool = false) {}
+  void begin(bool on_, bool keep = false) {  // (no events: the bytes handed to the exchange hook are still counted)
+    on = on_;
+    if (!keep) xbytes = 0, fft_kernels = 0;
+  }
   int start(int, emi_stream_t) { return -1; }
   void stop(int, emi_stream_t) {}
   void resolve(double *ms3, int *launches) {
@@ -4142,7 +4145,7 @@ TaskLayout task_layout(const Plan &P) {
   }
   return L;
 }
-int check_tasks(const Plan &P, const int *k, int nfld, const char *who) {
+int check_tasks(const Plan &P, const int *k, int nfld, const char *who, bool host_path = true) {
   // V-sets: a spectral field lives on the NPRTRW tasks of ONE V-set (KVSET of dist_spec.h / gath_spec.h), a grid field on the
   // sub-bands of all NPROC tasks; these re-layout helpers know the W-set decomposition only.  Hosts with NPRTRV > 1 move their
   // global fields themselves (TRANS_INQ gives every task's share: "latlo", "myms", "nasm0", "mysetv").
@@ -4150,8 +4153,9 @@ int check_tasks(const Plan &P, const int *k, int nfld, const char *who) {
   if (nfld < 0 || (nfld > 0 && !k)) EMI_FAIL(EMI_ERR_ARG, "%s: task list missing", who);
   for (int f = 0; f < nfld; f++)
     if (k[f] < 1 || k[f] > P.nproc) EMI_FAIL(EMI_ERR_ARG, "%s: task %d of field %d outside 1..%d", who, k[f], f + 1, P.nproc);
-  if (P.nproc > 1 && (!G.hc_bcast || !G.hc_gather))
+  if (host_path && P.nproc > 1 && (!G.hc_bcast || !G.hc_gather))
     EMI_FAIL(EMI_ERR_STATE, "%s: %d tasks but no host collectives registered (emi_set_host_collectives)", who, P.nproc);
+  if (!host_path && P.nproc > 1 && !G.a2a) EMI_FAIL(EMI_ERR_STATE, "%s: %d tasks but no all-to-all-v hook registered (emi_set_alltoallv)", who, P.nproc);
   return 0;
 }
 int slot_of(const int *ksort, int f, int nfld, const char *who, int *slot) {
@@ -4553,6 +4557,208 @@ static int agree_on_mixed_arrays(const char *who, int ndev, int nhost) {
     EMI_FAIL(EMI_ERR_ARG, "%s: %d ARRAYS OF THE CALL ARE IN DEVICE MEMORY AND %d IN HOST MEMORY (all of them must live in one place)", who, ndev, nhost);
   return 0;
 }
+// ------------------------------------------------------------------------------------------
+// DIST_* / GATH_* with the local array in device memory (emi_dist_spec_m ... emi_egath_grid_m).
+// Wire format of one chunk of fields: a task's send buffer holds one block per peer, in task order; a block holds the fields that
+// travel between the two tasks, ascending, each as the dense run of its elements on the task that holds the local side -- GATH_*:
+// the sender's nloc(me) elements of the fields whose target is the peer; DIST_*: the peer's nloc(t) elements of the fields whose
+// source is the sender.  One all-to-all-v per chunk moves every field once, to where it is wanted.  The local side is packed /
+// unpacked by k_spec_fields (PSPEC is field-fastest) or k_gridcopy (PGP is NPROMA-blocked); the global side by k_run_copy over
+// the runs of TaskLayout, straight into / out of the caller's global array where that lives in device memory, else through a
+// staged image and one copy per chunk.
+// ------------------------------------------------------------------------------------------
+static int gs_run_copy(Plan &P, const void *src, void *dst, std::vector<CopyRun> &runs, int nf, std::vector<StageBuf *> &keep, emi_stream_t st) {
+  if (runs.empty() || nf == 0) return 0;
+  long long nblk = 0;
+  for (CopyRun &r : runs) {
+    r.blk0 = (int)nblk;
+    nblk += (r.n + 255) / 256;
+  }
+  if (nblk * nf >= (1LL << 31)) EMI_FAIL(EMI_ERR_UNSUPPORTED, "global fields: %lld workgroups in one launch (lower EMI_GATH_CHUNK)", nblk * nf);
+  StageBuf *d = new StageBuf(runs.size() * sizeof(CopyRun));
+  keep.push_back(d);
+  if (!d->p || emi_h2d(d->p, runs.data(), runs.size() * sizeof(CopyRun), st)) EMI_FAIL(EMI_ERR_RUNTIME, "global fields: no device memory for %zu runs", runs.size());
+  EMI_LAUNCH_P(P.esz, k_run_copy, nblk * nf, 256, 0, st, (const RT *)src, (RT *)dst, (const CopyRun *)d->p, (int)runs.size(), (int)nblk, nf);
+  return 0;
+}
+// the local array <-> the dense fields [w][nloc] at `wire`; slots[w]: the field of PSPEC / PGP that is wire field w
+template <bool SPEC>
+static int gs_local(Plan &P, void *loc, void *wire, const std::vector<int> &slots, int nfld, long long nloc, int nproma, bool to_wire, std::vector<StageBuf *> &keep,
+                    emi_stream_t st) {
+  const int nf = (int)slots.size();
+  if (nf == 0 || nloc == 0) return 0;
+  if (SPEC) {
+    std::vector<SpecFld> tab(nf);
+    for (int w = 0; w < nf; w++) tab[w] = SpecFld{(long long)w * nloc, slots[w], 0};
+    StageBuf *d = new StageBuf(tab.size() * sizeof(SpecFld));
+    keep.push_back(d);
+    if (!d->p || emi_h2d(d->p, tab.data(), tab.size() * sizeof(SpecFld), st)) EMI_FAIL(EMI_ERR_RUNTIME, "spectral fields: no device memory for %d field descriptors", nf);
+    const long long ntf = (nf + SF_T - 1) / SF_T, nte = (nloc + SF_T - 1) / SF_T;
+    EMI_LAUNCH_P(P.esz, k_spec_fields, nte * ntf, 256, SF_LDS_BYTES(P.esz), st, (RT *)loc, (RT *)wire, (const SpecFld *)d->p, nfld, nf, nloc, (int)ntf,
+                 to_wire ? 1 : 0);
+    return 0;
+  }
+  std::vector<GridFld> arr, blk;
+  for (int w = 0; w < nf; w++) {
+    arr.push_back(GridFld{loc, nfld, slots[w], 0, 0});
+    blk.push_back(dense_field(wire, (size_t)w, nloc, P.esz));
+  }
+  return to_wire ? v_copy(P, arr, blk, 0, 0, nloc, nproma, nloc, keep, st) : v_copy(P, blk, arr, 0, 0, nloc, nloc, nproma, keep, st);
+}
+// gath: every task's share -> global fields on their targets; else global fields on their sources -> every task's share
+template <bool SPEC>
+static int gs_device(Plan &P, bool gath, void *glob, bool glob_dev, int nfld, const int *ktask, const int *ksort, int kproma, void *loc, const char *who) {
+  const TaskLayout L = task_layout(P);
+  const int esz = P.esz, NP = P.nproc, me = P.me, nproma = kproma > 0 ? kproma : P.ngptot;
+  const long long nglob = SPEC ? (long long)P.nspec2g : (long long)P.ngptotg;
+  auto nloc = [&](int t) { return SPEC ? L.nspec2[t] : L.ngp[t]; };
+  std::vector<int> slot(nfld);
+  for (int f = 0; f < nfld; f++)  // (KSORT and the presence of the global array: checked by gs_local_args before the tasks compared)
+    slot[f] = (gath || !ksort) ? f : ksort[f] - 1;
+  // the chunk rule of the host path, the same on every task: the global image of a chunk stays below 256 MiB / EMI_GATH_CHUNK
+  const long long per_field = nglob * (long long)esz;
+  const long long budget = (getenv("EMI_GATH_CHUNK") && *getenv("EMI_GATH_CHUNK")) ? atoll(getenv("EMI_GATH_CHUNK")) : (256LL << 20);
+  const int chunk = (int)std::max<long long>(1, std::min<long long>(nfld, budget / std::max<long long>(per_field, 1)));
+  const emi_stream_t st = (emi_stream_t)0;
+  if (plan_begin(P, st)) return EMI_ERR_RUNTIME;  // behind the last transform of the handle
+  g_pt.begin(G.profile != 0, G.profile == 2);
+  std::vector<long long> before(NP + 1, 0);  // elements of the tasks below t
+  for (int t = 0; t < NP; t++) before[t + 1] = before[t] + nloc(t);
+  long long i_mine = 0;
+  int rc = EMI_SUCCESS;
+  for (int fa = 0; fa < nfld && rc == EMI_SUCCESS; fa += chunk) {
+    const int nf = std::min(chunk, nfld - fa);
+    std::vector<int> order, cnt(NP, 0);  // the fields of the chunk by (peer, field); fields per peer
+    for (int t = 0; t < NP; t++)
+      for (int f = fa; f < fa + nf; f++)
+        if (ktask[f] == t + 1) order.push_back(f), cnt[t]++;
+    const int nmine = cnt[me];
+    std::vector<int> wslots;
+    for (int f : order) wslots.push_back(slot[f]);
+    // locb: the dense fields [w][nloc(me)] of the local side; globb: the blocks [task][field of mine][nloc(task)] of the global side
+    const size_t locbytes = (size_t)nf * nloc(me) * esz, globbytes = (size_t)nmine * nglob * esz;
+    StageBuf locb(locbytes), globb(NP > 1 ? globbytes : 0), img(glob_dev ? 0 : globbytes);
+    if ((locbytes && !locb.p) || (NP > 1 && globbytes && !globb.p) || (!glob_dev && globbytes && !img.p))
+      EMI_FAIL(EMI_ERR_RUNTIME, "%s: no device memory for the exchange buffers of %d fields", who, nf);
+    void *gb = NP > 1 ? globb.p : locb.p;  // one task: the two sides are one buffer, [field][nglob]
+    char *gcall = glob ? (char *)glob + (size_t)i_mine * nglob * esz : nullptr;
+    void *gimg = glob_dev ? (void *)gcall : img.p;
+    std::vector<StageBuf *> keep;
+    std::vector<CopyRun> runs;
+    for (int t = 0; t < NP && nmine; t++) {  // (global position, position in the block of task t) of every run
+      const long long boff = (long long)nmine * before[t];
+      if (SPEC) {
+        for (size_t k = 0; k < L.ms[t].size(); k++) {
+          const int m = L.ms[t][k];
+          if (L.mlen[m] > 0) runs.push_back(CopyRun{L.iasm0g[m], boff + L.start[t][k], nglob, nloc(t), (int)L.mlen[m], 0});
+        }
+      } else if (L.ngp[t] > 0) {
+        runs.push_back(CopyRun{L.gp0[t], boff, nglob, nloc(t), (int)L.ngp[t], 0});
+      }
+    }
+    std::vector<long long> cl(NP), cg(NP);  // bytes of the local-side and the global-side block with every task
+    for (int t = 0; t < NP; t++) cl[t] = (long long)cnt[t] * nloc(me) * esz, cg[t] = (long long)nmine * nloc(t) * esz;
+    bool bad;
+    if (gath) {
+      bad = gs_local<SPEC>(P, loc, locb.p, wslots, nfld, nloc(me), nproma, true, keep, st) || (NP > 1 && hook_alltoallv(locb.p, cl, gb, cg, NP, P.nprv, P.mev, st));
+      for (CopyRun &r : runs) std::swap(r.src0, r.dst0), std::swap(r.sfs, r.dfs);
+      bad = bad || gs_run_copy(P, gb, gimg, runs, nmine, keep, st) || (!glob_dev && globbytes && emi_d2h(gcall, gimg, globbytes, st));
+    } else {
+      bad = (!glob_dev && globbytes && emi_h2d(gimg, gcall, globbytes, st)) || gs_run_copy(P, gimg, gb, runs, nmine, keep, st) ||
+            (NP > 1 && hook_alltoallv(gb, cg, locb.p, cl, NP, P.nprv, P.mev, st)) || gs_local<SPEC>(P, loc, locb.p, wslots, nfld, nloc(me), nproma, false, keep, st);
+    }
+    if (emi_stream_sync(st) && !bad) {  // the call waits for its stream: the buffers go back to the pool, the caller needs no emi_wait
+      emi_set_error("%s: the kernels or copies of the call did not complete", who);
+      bad = true;
+    }
+    for (StageBuf *k : keep) delete k;
+    if (bad) rc = EMI_ERR_RUNTIME;
+    i_mine += nmine;
+  }
+  return rc;
+}
+static int gs_handle(int kresol, const char *who, bool lam, Plan **out) {
+  Plan *Pp = get_plan(kresol);
+  if (!Pp) EMI_FAIL(EMI_ERR_STATE, "%s: unknown resolution %d", who, kresol);
+  if (Pp->lam && !lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): this routine serves the spherical transforms only", who, kresol);
+  if (!Pp->lam && lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is not a limited-area handle: it was not set up by ESETUP_TRANS", who, kresol);
+  *out = Pp;
+  return 0;
+}
+// The local array alone selects the path; every task of a call must take the same one.  With registered host collectives the tasks
+// compare (one word each) and fail together; without them it is the caller's duty, as for EMI_MEM_AUTO of the transforms.
+// What one task alone can find wrong with the arguments of a device-path call, found BEFORE the tasks compare: a task that returned on its own
+// would leave its peers waiting in the exchange.  The message stays in the error text of this task.
+static int gs_local_args(const Plan &P, bool gath, const void *glob, int nfld, const int *ktask, const int *ksort, const void *loc, const char *who) {
+  if (check_tasks(P, ktask, nfld, who, false)) return EMI_ERR_ARG;
+  if (!loc) EMI_FAIL(EMI_ERR_ARG, "%s: local array missing", who);
+  int n_glob = 0, slot;
+  for (int f = 0; f < nfld; f++) {
+    if (!gath && slot_of(ksort, f, nfld, who, &slot)) return EMI_ERR_ARG;
+    if (ktask[f] == P.me + 1) n_glob++;
+  }
+  if (n_glob && !glob)
+    EMI_FAIL(EMI_ERR_ARG, gath ? "%s: this task is the target of %d fields but passes no global array" : "%s: this task is the source of %d fields but passes no global array", who, n_glob);
+  return 0;
+}
+// mine: 0 host path, 1 device path, 2 a device global array beside a host local array, 3 arguments refused on this task (gs_local_args)
+static int gs_agree_on_path(const char *who, int mine) {
+  std::vector<int> all(1, mine);
+  if (G.nproc_all > 1 && G.hc_gather) {
+    const int NA = G.nproc_all;
+    all.assign(NA, 0);
+    std::vector<long long> cnt(NA, 4), dsp(NA);
+    for (int r = 0; r < NA; r++) dsp[r] = 4LL * r;
+    if (G.hc_gather(G.hc_user, &mine, 4, all.data(), cnt.data(), dsp.data(), NA)) EMI_FAIL(EMI_ERR_RUNTIME, "%s: all-gather-v failed", who);
+  }
+  if (mine == 3) return EMI_ERR_ARG;  // (with this task's own message)
+  for (size_t r = 0; r < all.size(); r++)
+    if (all[r] == 3) EMI_FAIL(EMI_ERR_ARG, "%s: TASK %d REFUSED ITS ARGUMENTS (its error text says why); no task of the call went on", who, (int)r + 1);
+  for (size_t r = 0; r < all.size(); r++)
+    if (all[r] == 2)
+      EMI_FAIL(EMI_ERR_ARG, "%s: THE GLOBAL ARRAY IS IN DEVICE MEMORY AND THE LOCAL ARRAY IN HOST MEMORY ON TASK %d (a host local array takes the host path)", who,
+               all.size() > 1 ? (int)r + 1 : G.myproc_all);
+  for (size_t r = 0; r < all.size(); r++)
+    if (all[r] != mine)
+      EMI_FAIL(EMI_ERR_ARG, "%s: THE LOCAL ARRAY IS IN %s MEMORY HERE AND IN %s MEMORY ON TASK %d (every task of a call must take the same path)", who,
+               mine ? "DEVICE" : "HOST", mine ? "HOST" : "DEVICE", (int)r + 1);
+  return 0;
+}
+template <bool SPEC>
+static int gs_m(bool gath, int kresol, int glob_space, const void *glob, int nfld, const int *ktask, const int *ksort, int kproma, int loc_space, const void *loc,
+                const char *who, bool lam) {
+  Plan *Pp;
+  if (int rc = gs_handle(kresol, who, lam, &Pp)) return rc;
+  for (int sp : {glob_space, loc_space})
+    if (sp != EMI_MEM_HOST && sp != EMI_MEM_DEVICE && sp != EMI_MEM_AUTO)
+      EMI_FAIL(EMI_ERR_ARG, "%s: memory space %d (EMI_MEM_HOST, EMI_MEM_DEVICE or EMI_MEM_AUTO)", who, sp);
+  if (glob_space == EMI_MEM_AUTO) glob_space = emi_ptr_space(glob);
+  if (loc_space == EMI_MEM_AUTO) loc_space = emi_ptr_space(loc);
+  const bool glob_dev = glob && glob_space == EMI_MEM_DEVICE, loc_dev = loc_space == EMI_MEM_DEVICE;
+  if (Pp->nprv > 1) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: not available with NPRTRV > 1", who);
+  const int word = (!loc_dev && glob_dev) ? 2 : !loc_dev ? 0 : gs_local_args(*Pp, gath, glob, nfld, ktask, ksort, loc, who) ? 3 : 1;
+  if (gs_agree_on_path(who, word)) return EMI_ERR_ARG;
+  if (!loc_dev)
+    return gath ? gath_impl<SPEC>(kresol, (void *)glob, nfld, ktask, kproma, loc, who, lam) : dist_impl<SPEC>(kresol, glob, nfld, ktask, ksort, kproma, (void *)loc, who, lam);
+  return gs_device<SPEC>(*Pp, gath, (void *)glob, glob_dev, nfld, ktask, ksort, kproma, (void *)loc, who);
+}
+#define EMI_GS_M(pre, PRE, lam)                                                                                                                                          \
+  extern "C" int emi_##pre##dist_spec_m(int kresol, int glob_space, const void *specg, int nfld, const int *kfrom, const int *ksort, int loc_space, void *spec) {          \
+    return gs_m<true>(false, kresol, glob_space, specg, nfld, kfrom, ksort, 0, loc_space, spec, PRE "DIST_SPEC", lam);                                                    \
+  }                                                                                                                                                                        \
+  extern "C" int emi_##pre##gath_spec_m(int kresol, int glob_space, void *specg, int nfld, const int *kto, int loc_space, const void *spec) {                             \
+    return gs_m<true>(true, kresol, glob_space, specg, nfld, kto, nullptr, 0, loc_space, spec, PRE "GATH_SPEC", lam);                                                     \
+  }                                                                                                                                                                        \
+  extern "C" int emi_##pre##dist_grid_m(int kresol, int glob_space, const void *gpg, int nfld, const int *kfrom, const int *ksort, int kproma, int loc_space, void *gp) { \
+    return gs_m<false>(false, kresol, glob_space, gpg, nfld, kfrom, ksort, kproma, loc_space, gp, PRE "DIST_GRID", lam);                                                  \
+  }                                                                                                                                                                        \
+  extern "C" int emi_##pre##gath_grid_m(int kresol, int glob_space, void *gpg, int nfld, const int *kto, int kproma, int loc_space, const void *gp) {                     \
+    return gs_m<false>(true, kresol, glob_space, gpg, nfld, kto, nullptr, kproma, loc_space, gp, PRE "GATH_GRID", lam);                                                   \
+  }
+EMI_GS_M(, "", false)
+EMI_GS_M(e, "E", true)
+#undef EMI_GS_M
+
 template <class A>
 static int resolve_call(const char *who, const A *ap, A &a) {
   if (!ap) EMI_FAIL(EMI_ERR_ARG, "%s: null argument block", who);

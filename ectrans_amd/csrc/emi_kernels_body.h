@@ -3064,6 +3064,75 @@ EMI_KERNEL_LB(256) void k_gridcopy(const GridFld *src, const GridFld *dst, int n
 }
 
 // ==========================================================================================
+// k_spec_fields: DIST_SPEC / GATH_SPEC on device arrays.  PSPEC(nfld, nspec2) is field-fastest, the exchange buffers hold every
+// field as a dense run of its elements: a transpose.  One workgroup moves a tile of 64 elements x 64 fields through LDS, so that
+// both sides are read and written along their fastest index (lanes = fields on the PSPEC side, lanes = elements on the buffer
+// side).  The tile is kept as 32-bit words, one plane per word of a real, rows of 65 words: lane l touches word 65 r + l on one
+// side and 65 l + c on the other, 32 consecutive lanes on 32 different banks either way.  to_wire: PSPEC -> buffer (GATH_SPEC),
+// else buffer -> PSPEC (DIST_SPEC); tab[j]: the slot in PSPEC and the first buffer element of field j.  Tiles at the end of
+// either direction are partial; a slot no field of the call names is never written.
+// ==========================================================================================
+#define SF_T 64
+#define SF_RS (SF_T + 1)
+static_assert(256 % SF_T == 0 && SF_RS % 2 == 1, "k_spec_fields: 256 threads cover whole tile rows; rows of an odd word count");
+#define SF_LDS_BYTES(esz) ((size_t)((esz) / 4) * SF_T * SF_RS * 4)  // of a launch: one plane of SF_T rows per 32-bit word of a real
+EMI_DEVFN void sf_put(unsigned *t, int idx, real_t v) {
+  unsigned u[sizeof(real_t) / 4];
+  __builtin_memcpy(u, &v, sizeof(real_t));
+  for (int w = 0; w < (int)(sizeof(real_t) / 4); w++) t[w * (SF_T * SF_RS) + idx] = u[w];
+}
+EMI_DEVFN real_t sf_get(const unsigned *t, int idx) {
+  unsigned u[sizeof(real_t) / 4];
+  for (int w = 0; w < (int)(sizeof(real_t) / 4); w++) u[w] = t[w * (SF_T * SF_RS) + idx];
+  real_t v;
+  __builtin_memcpy(&v, u, sizeof(real_t));
+  return v;
+}
+EMI_KERNEL_LB(256) void k_spec_fields(real_t *pspec, real_t *wire, const SpecFld *tab, int nfld_arr, int nf, long long nel, int ntf, int to_wire) {
+  EMI_LDS_DECL;
+  unsigned *t = (unsigned *)EMI_LDS_PTR;
+  const int tf = EMI_BID % ntf, te = EMI_BID / ntf;
+  const long long e0 = (long long)te * SF_T;
+  const int f0 = tf * SF_T, lo = EMI_TID % SF_T, hi = EMI_TID / SF_T;
+  const int jf = f0 + lo;          // PSPEC side: this lane's field
+  const long long el = e0 + lo;    // buffer side: this lane's element
+  const int slot = jf < nf ? tab[jf].slot : 0;
+  if (to_wire) {
+    for (int r = hi; r < SF_T; r += 256 / SF_T)
+      if (jf < nf && e0 + r < nel) sf_put(t, r * SF_RS + lo, pspec[(e0 + r) * nfld_arr + slot]);
+    EMI_SYNC();
+    for (int c = hi; c < SF_T; c += 256 / SF_T)
+      if (f0 + c < nf && el < nel) wire[tab[f0 + c].woff + el] = sf_get(t, lo * SF_RS + c);
+  } else {
+    for (int c = hi; c < SF_T; c += 256 / SF_T)
+      if (f0 + c < nf && el < nel) sf_put(t, lo * SF_RS + c, wire[tab[f0 + c].woff + el]);
+    EMI_SYNC();
+    for (int r = hi; r < SF_T; r += 256 / SF_T)
+      if (jf < nf && e0 + r < nel) pspec[(e0 + r) * nfld_arr + slot] = sf_get(t, r * SF_RS + lo);
+  }
+}
+
+// ==========================================================================================
+// k_run_copy: the global side of DIST_* / GATH_* on device arrays.  A global field is cut into contiguous runs -- the coefficients
+// of one zonal wavenumber, the grid points of one task's band -- that lie somewhere else in the exchange buffer of the task that
+// owns them.  runs[]: the runs of one field, built on the host from the task layout, ascending in blk0; field f adds its strides.
+// One workgroup copies 256 elements of one run of one field; it finds its run by bisection on blk0 (uniform over the workgroup).
+// ==========================================================================================
+EMI_KERNEL_LB(256) void k_run_copy(const real_t *src, real_t *dst, const CopyRun *runs, int nruns, int nblk, int nf) {
+  const int f = EMI_BID / nblk, b = EMI_BID - f * nblk;
+  if (f >= nf) return;
+  int lo = 0, hi = nruns - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (runs[mid].blk0 <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  const CopyRun r = runs[lo];
+  const int i = (b - r.blk0) * 256 + EMI_TID;
+  if (i < r.n) dst[r.dst0 + f * r.dfs + i] = src[r.src0 + f * r.sfs + i];
+}
+
+// ==========================================================================================
 // k_legpol: SUPOLF (supolf_mod.F90:13-251) for m >= 2 on the device -- the normalised associated
 // Legendre functions P_n^m(mu), n = m+par, m+par+2, ..., of one (wavenumber, parity, latitude) per
 // thread, by the reference's 4-term recurrence in n with its 1e+-100 rescaling, written straight into

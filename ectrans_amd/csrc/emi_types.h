@@ -98,6 +98,15 @@ struct GridFld {  // one Fourier-space field <-> one user grid field
   int nf_arr, fidx;
   int mode, src;  // src: field index inside FB (inverse only)
 };
+// DIST_* / GATH_* on device arrays (k_spec_fields, k_run_copy)
+struct SpecFld {   // one field of PSPEC(nfld, nspec2) <-> its dense [element] image in an exchange buffer
+  long long woff;  // first element of the image in the buffer
+  int slot, pad;   // the field's index in PSPEC
+};
+struct CopyRun {  // n contiguous elements of field f: src[src0 + f sfs + i] -> dst[dst0 + f dfs + i]
+  long long src0, dst0, sfs, dfs;
+  int n, blk0;  // blk0: first 256-element block of the run among the blocks of one field
+};
 
 struct FftPlanDev {
   int n;      // row length (NLOEN)

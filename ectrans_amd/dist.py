@@ -25,18 +25,20 @@ _keep = []
 class _DeviceBuffer:
     """Zero-copy view of raw device memory for torch.as_tensor (CUDA array interface v2)."""
 
-    def __init__(self, ptr, nelem):
-        self.__cuda_array_interface__ = {"shape": (nelem,), "typestr": "<f8", "data": (int(ptr), False), "version": 2}
+    def __init__(self, ptr, nbytes):
+        self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
 
 
 def _as_tensor(ptr, nbytes, device):
+    """the bytes of a buffer of the library as a uint8 tensor: the same element type on every task whatever the blocks hold (the
+    transforms' rows are multiples of 16 bytes, the blocks of DIST_x / GATH_x on device arrays any number of fp64 or fp32 reals)"""
     import torch
-    n = int(nbytes) // 8
+    n = int(nbytes)
     if n == 0:
-        return torch.empty(0, dtype=torch.float64, device=device)
+        return torch.empty(0, dtype=torch.uint8, device=device)
     if device.type == "cuda":
         return torch.as_tensor(_DeviceBuffer(ptr, n), device=device)
-    arr = np.ctypeslib.as_array((C.c_double * n).from_address(int(ptr)))
+    arr = np.ctypeslib.as_array((C.c_uint8 * n).from_address(int(ptr)))
     return torch.from_numpy(arr)
 
 
@@ -90,7 +92,7 @@ def make_alltoallv_hook(group=None, device=None, p2p=False):
             assert all(sdl[i] == sum(scl[:i]) for i in range(nproc)) and all(rdl[i] == sum(rcl[:i]) for i in range(nproc))
             send = _as_tensor(sb, sum(scl), device)
             recv = _as_tensor(rb, sum(rcl), device)
-            osz, isz = [c // 8 for c in rcl], [c // 8 for c in scl]
+            osz, isz = rcl, scl  # bytes
             if staged:
                 # test configuration only (several ranks sharing one GPU, gloo has no device
                 # all-to-all): stage through the host, ordered on the stream the library passed -- only

@@ -31,19 +31,25 @@ static int hook(void *user, const void *sendbuf, const long long *sc, const long
   int *isc = malloc(sizeof(int) * 4 * (size_t)nproc), *isd = isc + nproc, *irc = isd + nproc, *ird = irc + nproc;
   long long stot = 0, rtot = 0;
   int rcode = 0;
-  /* MPI counts are ints: exchange in units of 16 bytes (every block is a multiple of a complex fp64 /
-   * of two complex fp32 numbers) */
+  /* MPI counts are ints: exchange in the largest unit of 16, 8, 4, 2 or 1 bytes that divides every count and displacement of this
+   * task.  The blocks of the transforms are multiples of 16 (a complex fp64 / two complex fp32 numbers); those of DIST_x / GATH_x on
+   * device arrays are any number of reals.  The unit may differ between two tasks: the type signature of a message is its bytes. */
+  long long all = 0;
+  for (int r = 0; r < nproc; r++) all |= sc[r] | sd[r] | rc[r] | rd[r];
+  int unit = 16;
+  while (unit > 1 && (all & (unit - 1))) unit >>= 1;
   for (int r = 0; r < nproc; r++) {
-    if ((sc[r] | sd[r] | rc[r] | rd[r]) & 15 || sc[r] / 16 > 2147483647LL || sd[r] / 16 > 2147483647LL || rd[r] / 16 > 2147483647LL) {
+    if (sc[r] < 0 || sd[r] < 0 || rc[r] < 0 || rd[r] < 0 || sc[r] / unit > 2147483647LL || sd[r] / unit > 2147483647LL || rc[r] / unit > 2147483647LL ||
+        rd[r] / unit > 2147483647LL) {
       free(isc);
       return -1;
     }
-    isc[r] = (int)(sc[r] / 16), isd[r] = (int)(sd[r] / 16), irc[r] = (int)(rc[r] / 16), ird[r] = (int)(rd[r] / 16);
+    isc[r] = (int)(sc[r] / unit), isd[r] = (int)(sd[r] / unit), irc[r] = (int)(rc[r] / unit), ird[r] = (int)(rd[r] / unit);
     if (sd[r] + sc[r] > stot) stot = sd[r] + sc[r];
     if (rd[r] + rc[r] > rtot) rtot = rd[r] + rc[r];
   }
-  MPI_Datatype t16;
-  MPI_Type_contiguous(16, MPI_BYTE, &t16);
+  MPI_Datatype t16; /* (the unit) */
+  MPI_Type_contiguous(unit, MPI_BYTE, &t16);
   MPI_Type_commit(&t16);
   /* With V-sets the exchanges run inside a V-set (TRMTOL / TRLTOM) or inside a W-set (TRLTOG / TRGTOL), and two V-sets need not make
    * the same number of calls (their field counts differ, one may hold none): a collective over all tasks cannot take that, so

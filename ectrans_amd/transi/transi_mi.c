@@ -593,21 +593,30 @@ int trans_distgrid(struct DistGrid_t *a) {
   if (!a->trans || !a->rgp || !a->nfrom || a->nfld <= 0 || a->nproma <= 0) return TRANS_MISSING_ARG;
   const long ng = a->trans->ngptot, np = a->nproma, nb = (ng - 1) / np + 1;
   if (a->ngpblks < nb) return TRANS_ERROR;
-  if ((a->trans->llam ? emi_edist_grid : emi_dist_grid)(a->trans->handle, a->rgpg, a->nfld, a->nfrom, NULL, a->nproma, a->rgp)) return TRANS_ERROR;
+  /* each array where it lives (EMI_MEM_AUTO): a hipMalloc'ed rgp takes the device path of the library, in place */
+  if ((a->trans->llam ? emi_edist_grid_m : emi_dist_grid_m)(a->trans->handle, EMI_MEM_AUTO, a->rgpg, a->nfld, a->nfrom, NULL, a->nproma, EMI_MEM_AUTO, a->rgp))
+    return TRANS_ERROR;
   /* the padding of the last NPROMA block (and any further block): zero, as the Fortran DIST_GRID of the shim leaves it -- a
    * malloc'ed rgp must not carry NaNs into a later trans_dirtrans or a checksum */
+  const int dev = emi_ptr_space(a->rgp) == EMI_MEM_DEVICE;
   for (long b = nb - 1; b < a->ngpblks; b++) {
     const long first = b == nb - 1 ? ng - (nb - 1) * np : 0;
-    for (int f = 0; f < a->nfld; f++) memset(a->rgp + ((size_t)b * a->nfld + f) * np + first, 0, sizeof(double) * (size_t)(np - first));
+    for (int f = 0; f < a->nfld; f++) {
+      double *pad = a->rgp + ((size_t)b * a->nfld + f) * np + first;
+      if (!dev) memset(pad, 0, sizeof(double) * (size_t)(np - first));
+      else if (np > first && hipMemset(pad, 0, sizeof(double) * (size_t)(np - first)) != hipSuccess) return TRANS_ERROR;
+    }
   }
   return TRANS_SUCCESS;
 }
 int trans_gathgrid(struct GathGrid_t *a) {
   if (a->count++ > 0) return TRANS_STALE_ARG;
   if (!a->trans || !a->rgp || !a->nto || a->nfld <= 0 || a->nproma <= 0) return TRANS_MISSING_ARG;
-  return (a->trans->llam ? emi_egath_grid : emi_gath_grid)(a->trans->handle, a->rgpg, a->nfld, a->nto, a->nproma, a->rgp) ? TRANS_ERROR : TRANS_SUCCESS;
+  return (a->trans->llam ? emi_egath_grid_m : emi_gath_grid_m)(a->trans->handle, EMI_MEM_AUTO, a->rgpg, a->nfld, a->nto, a->nproma, EMI_MEM_AUTO, a->rgp) ? TRANS_ERROR
+                                                                                                                                                        : TRANS_SUCCESS;
 }
-/* rspecg is [nspec2g][nfldg] here (Fortran PSPECG(nfldg, nspec2g), transi.h:1140-1186), [nfldg][nspec2g] in the C-ABI */
+/* rspecg is [nspec2g][nfldg] here (Fortran PSPECG(nfldg, nspec2g), transi.h:1140-1186), [nfldg][nspec2g] in the C-ABI: it goes through a
+ * transposed host copy, so rspecg itself must be a host array; rspec is used where it lives (EMI_MEM_AUTO) */
 static int count_mine(const struct Trans_t *t, const int *task, int nfld) {
   int n = 0;
   for (int f = 0; f < nfld; f++) n += task[f] == t->myproc;
@@ -621,12 +630,13 @@ int trans_distspec(struct DistSpec_t *a) {
   double *tmp = NULL;
   if (nm > 0) {
     if (!a->rspecg) return TRANS_MISSING_ARG;
+    if (emi_ptr_space(a->rspecg) == EMI_MEM_DEVICE) return TRANS_ERROR;
     tmp = (double *)malloc(sizeof(double) * ng * (size_t)nm);
     if (!tmp) return TRANS_ERROR;
     for (size_t i = 0; i < ng; i++)
       for (int f = 0; f < nm; f++) tmp[(size_t)f * ng + i] = a->rspecg[i * (size_t)nm + f];
   }
-  const int rc = (a->trans->llam ? emi_edist_spec : emi_dist_spec)(a->trans->handle, tmp, a->nfld, a->nfrom, NULL, a->rspec);
+  const int rc = (a->trans->llam ? emi_edist_spec_m : emi_dist_spec_m)(a->trans->handle, EMI_MEM_AUTO, tmp, a->nfld, a->nfrom, NULL, EMI_MEM_AUTO, a->rspec);
   free(tmp);
   return rc ? TRANS_ERROR : TRANS_SUCCESS;
 }
@@ -638,10 +648,11 @@ int trans_gathspec(struct GathSpec_t *a) {
   double *tmp = NULL;
   if (nm > 0) {
     if (!a->rspecg) return TRANS_MISSING_ARG;
+    if (emi_ptr_space(a->rspecg) == EMI_MEM_DEVICE) return TRANS_ERROR;
     tmp = (double *)malloc(sizeof(double) * ng * (size_t)nm);
     if (!tmp) return TRANS_ERROR;
   }
-  const int rc = (a->trans->llam ? emi_egath_spec : emi_gath_spec)(a->trans->handle, tmp, a->nfld, a->nto, a->rspec);
+  const int rc = (a->trans->llam ? emi_egath_spec_m : emi_gath_spec_m)(a->trans->handle, EMI_MEM_AUTO, tmp, a->nfld, a->nto, EMI_MEM_AUTO, a->rspec);
   if (!rc)
     for (size_t i = 0; i < ng; i++)
       for (int f = 0; f < nm; f++) a->rspecg[i * (size_t)nm + f] = tmp[(size_t)f * ng + i];

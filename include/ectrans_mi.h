@@ -342,7 +342,7 @@ int emi_specnorm_partial(int kresol, int mem_space, const void *spec, int nfld, 
 /* ---- DIST_SPEC / GATH_SPEC / DIST_GRID / GATH_GRID (trans/include/ectrans/dist_spec.h, gath_spec.h, dist_grid.h,
  * gath_grid.h; trans/cpu/internal/dist_spec_control_mod.F90, gath_spec_control_mod.F90, dist_grid_ctl_mod.F90,
  * gath_grid_ctl_mod.F90) -- global fields on single tasks <-> the distributed arrays of the transforms.  HOST arrays
- * of the resolution's precision, not on the transform path.  Global spectral order: m = 0..N, n = m..N, (re, im)
+ * of the resolution's precision, not on the transform path (device-resident fields: the _m entry points below).  Global spectral order: m = 0..N, n = m..N, (re, im)
  * (dist_spec_control_mod.F90:158-161); global grid order: latitudes north to south = the tasks' bands in task order.
  *   specg / gpg : the global fields this task is the source (kfrom[f] == myproc) or the target (kto[f] == myproc) of,
  *                 one after the other in field order: [n_mine][nspec2g] / [n_mine][ngptotg]  (= PGPG(ngptotg, n_mine))
@@ -366,6 +366,27 @@ int emi_edist_spec(int kresol, const void *specg, int nfld, const int *kfrom, co
 int emi_egath_spec(int kresol, void *specg, int nfld, const int *kto, const void *spec);
 int emi_edist_grid(int kresol, const void *gpg, int nfld, const int *kfrom, const int *ksort, int kproma, void *gp);
 int emi_egath_grid(int kresol, void *gpg, int nfld, const int *kto, int kproma, const void *gp);
+/* The same eight with a memory space per array: layouts, kfrom / kto / ksort, the handle checks and NPRTRV = 1 as above.
+ * glob_space, loc_space: EMI_MEM_HOST, EMI_MEM_DEVICE or EMI_MEM_AUTO (emi_ptr_space of that array); unlike the transforms the two
+ * arrays of a call may live in different memories (a host I/O image beside device-resident fields).  The LOCAL array selects the path:
+ *   host   : the routines above, unchanged (host collectives); a device global array beside it is EMI_ERR_ARG.
+ *   device : the local share is packed on the device (PSPEC by a tiled transpose, PGP by blocks), ONE all-to-all-v per chunk of
+ *            fields (the hook of emi_set_alltoallv, on the stream of the handle behind its last transform) sends every field to its
+ *            target / from its source only, and the global side is laid out on the device -- straight into / out of the caller's
+ *            global array where that is in device memory, else through a staged image and one copy per chunk.  Scratch comes from
+ *            the staging pool (EMI_STAGE_POOL, emi_trim_cache).  The call returns when its stream has drained: no emi_wait is
+ *            needed.  Several tasks without a hook: EMI_ERR_STATE.  With emi_set_profile the exchange is counted by
+ *            emi_last_exchange.  A chunk is the fields whose global images stay below 256 MiB (EMI_GATH_CHUNK, bytes).
+ * Every task of a call must take the same path.  With registered host collectives the tasks compare and fail together; without
+ * them (a host that drives the exchange hook only) that is the caller's duty, as for EMI_MEM_AUTO of the transforms.            */
+int emi_dist_spec_m(int kresol, int glob_space, const void *specg, int nfld, const int *kfrom, const int *ksort, int loc_space, void *spec);
+int emi_gath_spec_m(int kresol, int glob_space, void *specg, int nfld, const int *kto, int loc_space, const void *spec);
+int emi_dist_grid_m(int kresol, int glob_space, const void *gpg, int nfld, const int *kfrom, const int *ksort, int kproma, int loc_space, void *gp);
+int emi_gath_grid_m(int kresol, int glob_space, void *gpg, int nfld, const int *kto, int kproma, int loc_space, const void *gp);
+int emi_edist_spec_m(int kresol, int glob_space, const void *specg, int nfld, const int *kfrom, const int *ksort, int loc_space, void *spec);
+int emi_egath_spec_m(int kresol, int glob_space, void *specg, int nfld, const int *kto, int loc_space, const void *spec);
+int emi_edist_grid_m(int kresol, int glob_space, const void *gpg, int nfld, const int *kfrom, const int *ksort, int kproma, int loc_space, void *gp);
+int emi_egath_grid_m(int kresol, int glob_space, void *gpg, int nfld, const int *kto, int kproma, int loc_space, const void *gp);
 /* What emi_init was given (EMI_ERR_STATE before it): a Fortran host whose transport attached first (emi_mpi_attach,
  * emi_rccl_attach) learns its task number from here in SETUP_TRANS0.                                                 */
 int emi_inq_tasks(int *nproc, int *myproc);
