@@ -159,6 +159,9 @@ def _bind(L):
             getattr(L, "emi_%sgath_spec_m" % e).argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, ip, C.c_int, C.c_void_p]
             getattr(L, "emi_%sdist_grid_m" % e).argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, ip, ip, C.c_int, C.c_int, C.c_void_p]
             getattr(L, "emi_%sgath_grid_m" % e).argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, ip, C.c_int, C.c_int, C.c_void_p]
+    if hasattr(L, "emi_dist_spec_v"):  # (an older build loaded for an A/B run)
+        L.emi_dist_spec_v.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, ip, ip, ip, C.c_int, C.c_void_p]
+        L.emi_gath_spec_v.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, ip, ip, C.c_int, C.c_void_p]
     L.emi_inq_init.argtypes = [ip, dp]
     L.emi_set_nprtrv.argtypes = [C.c_int]
     if hasattr(L, "emi_esetup"):  # (an older build loaded for an A/B run)
@@ -1032,18 +1035,30 @@ def _gs_spaces(who, mem_space, glob_space, glob=None):
     return ls, gs
 
 
-def dist_spec(kresol, pspecg, kfdistg, kfrom=1, mem_space=None, glob_space=None):
+def _kvset_local(kresol, kvset, nfld, who):
+    """(kvset as int32, fields of PSPEC on this task): with NPRTRV > 1 the fields whose V-set is this task's, else all of them"""
+    kv = np.ascontiguousarray(kvset, dtype=np.int32)
+    if kv.shape != (nfld,):
+        raise TransError("%s: KVSET must name the V-set of each of the %d fields" % (who, nfld))
+    if trans_inq(kresol, "nprtrv") == 1:
+        return kv, nfld
+    return kv, int((kv == trans_inq(kresol, "mysetv")).sum())
+
+
+def dist_spec(kresol, pspecg, kfdistg, kfrom=1, mem_space=None, glob_space=None, kvset=None):
     """DIST_SPEC (dist_spec.h:11) over emi_dist_spec: global spectral fields `pspecg` (nspec2g, kfdistg), field f held
     by task kfrom[f] (1-based; the columns of other tasks' fields are not read, the array may be None on a task that is
     the source of none), -> this task's (nspec2, kfdistg) local array.
+    kvset (NPRTRV > 1, emi_dist_spec_v): the V-set of every one of the kfdistg GLOBAL fields; the result holds the fields of this
+    task's own V-set, (nspec2, COUNT(kvset == mysetv)), which may be no field at all.  kfrom[f] may be any of the NPRTRW x NPRTRV tasks.
     mem_space=EMI_MEM_DEVICE (emi_dist_spec_m): the local array is laid out on the device and returned as a device tensor (a numpy
     array on the CPU emulator of the tests); glob_space: the memory the global image is consumed from (default: where `pspecg` lives).
     The local array is created by the call, so there is nothing for EMI_MEM_AUTO to classify: mem_space=EMI_MEM_AUTO, and glob_space=
     given alone, mean EMI_MEM_DEVICE; only mem_space=EMI_MEM_HOST gives a numpy result through the host path."""
-    return _dist_spec("", kresol, pspecg, kfdistg, kfrom, None, mem_space, glob_space)
+    return _dist_spec("", kresol, pspecg, kfdistg, kfrom, None, mem_space, glob_space, kvset)
 
 
-def _dist_spec(_e, kresol, pspecg, kfdistg, kfrom, ksort, mem_space=None, glob_space=None):
+def _dist_spec(_e, kresol, pspecg, kfdistg, kfrom, ksort, mem_space=None, glob_space=None, kvset=None):
     """dist_spec (_e = "") / edist_spec (_e = "e")"""
     dt = real_dtype(kresol)
     ns2g, ns2, me = trans_inq(kresol, "nspec2g"), trans_inq(kresol, "nspec2"), trans_inq(kresol, "myproc")
@@ -1051,16 +1066,19 @@ def _dist_spec(_e, kresol, pspecg, kfdistg, kfrom, ksort, mem_space=None, glob_s
     kfrom = _roots(kfrom, kfdistg, who + ":KFROM")
     mine = np.flatnonzero(kfrom == me)
     ks = None if ksort is None else np.ascontiguousarray(ksort, dtype=np.int32)
-    if mem_space is not None or glob_space is not None:
-        ls, gs = _gs_spaces(who, mem_space, glob_space, pspecg)
+    kv, nfl = (None, kfdistg) if kvset is None else _kvset_local(kresol, kvset, kfdistg, who)
+    if mem_space is not None or glob_space is not None or kv is not None:
+        host = mem_space is None and glob_space is None  # (kvset alone: host arrays through the general entry point)
+        ls, gs = (EMI_MEM_HOST, EMI_MEM_HOST) if host else _gs_spaces(who, mem_space, glob_space, pspecg)
         g = None
         if mine.size:
             if pspecg.shape[0] != ns2g:
                 raise TransError("%s: PSPECG must have shape (nspec2g=%d, nfld)" % (who, ns2g))
             g = _gs_move(pspecg[:, mine.tolist()].T, dt, gs == EMI_MEM_DEVICE)  # [n_mine][nspec2g]
-        out = _gs_zeros((ns2, kfdistg), dt, ls != EMI_MEM_HOST, pspecg)
-        _chk(getattr(lib(), "emi_%sdist_spec_m" % _e)(kresol, gs, _gs_ptr(g, dt, who, "PSPECG"), kfdistg, _iptr(kfrom), None if ks is None else _iptr(ks),
-                                                      EMI_MEM_HOST if ls == EMI_MEM_HOST else EMI_MEM_DEVICE, _gs_ptr(out, dt, who, "PSPEC")))
+        out = _gs_zeros((ns2, nfl), dt, ls != EMI_MEM_HOST, pspecg)
+        a = (kresol, gs, _gs_ptr(g, dt, who, "PSPECG"), kfdistg, _iptr(kfrom))
+        b = (None if ks is None else _iptr(ks), EMI_MEM_HOST if ls == EMI_MEM_HOST else EMI_MEM_DEVICE, _gs_ptr(out, dt, who, "PSPEC") if nfl else None)
+        _chk(getattr(lib(), "emi_%sdist_spec_m" % _e)(*a, *b) if kv is None else lib().emi_dist_spec_v(*a, _iptr(kv), *b))
         return out
     g = None
     if mine.size:
@@ -1074,28 +1092,38 @@ def _dist_spec(_e, kresol, pspecg, kfdistg, kfrom, ksort, mem_space=None, glob_s
     return out
 
 
-def gath_spec(kresol, pspec, kfgathg, kto=1, mem_space=None, glob_space=None):
+def gath_spec(kresol, pspec, kfgathg, kto=1, mem_space=None, glob_space=None, kvset=None):
     """GATH_SPEC (gath_spec.h:11) over emi_gath_spec: local (nspec2, kfgathg) -> global (nspec2g, n_mine) holding the
     fields this task is the target of (None if it is the target of none).
+    kvset (NPRTRV > 1, emi_gath_spec_v): the V-set of every one of the kfgathg GLOBAL fields; `pspec` holds the fields of this task's
+    own V-set, (nspec2, COUNT(kvset == mysetv)), and may be None on a task whose V-set owns none (it still takes part).
     mem_space=EMI_MEM_DEVICE (emi_gath_spec_m): `pspec` is a contiguous device tensor used in place (a numpy array on the CPU emulator
     of the tests); glob_space: the memory of the returned global image (default host: a numpy array; EMI_MEM_DEVICE: a device
     tensor, the (nspec2g, n_mine) view of the [n_mine][nspec2g] image)."""
-    return _gath_spec("", kresol, pspec, kfgathg, kto, mem_space, glob_space)
+    return _gath_spec("", kresol, pspec, kfgathg, kto, mem_space, glob_space, kvset)
 
 
-def _gath_spec(_e, kresol, pspec, kfgathg, kto, mem_space=None, glob_space=None):
+def _gath_spec(_e, kresol, pspec, kfgathg, kto, mem_space=None, glob_space=None, kvset=None):
     """gath_spec (_e = "") / egath_spec (_e = "e")"""
     dt = real_dtype(kresol)
     ns2g, me = trans_inq(kresol, "nspec2g"), trans_inq(kresol, "myproc")
     who = _e.upper() + "GATH_SPEC"
     kto = _roots(kto, kfgathg, who + ":KTO")
     nm = int((kto == me).sum())
-    if mem_space is not None or glob_space is not None:
-        ls, gs = _gs_spaces(who, mem_space, glob_space)
-        if pspec.ndim != 2 or pspec.shape[1] != kfgathg or pspec.shape[0] != trans_inq(kresol, "nspec2"):
-            raise TransError("%s: PSPEC must have shape (nspec2, kfgathg=%d)" % (who, kfgathg))
+    kv, nfl = (None, kfgathg) if kvset is None else _kvset_local(kresol, kvset, kfgathg, who)
+    if mem_space is not None or glob_space is not None or kv is not None:
+        host = mem_space is None and glob_space is None  # (kvset alone: host arrays through the general entry point)
+        ls, gs = (EMI_MEM_HOST, EMI_MEM_HOST) if host else _gs_spaces(who, mem_space, glob_space)
+        if host and pspec is not None:
+            pspec = np.ascontiguousarray(_np(pspec), dtype=dt)
+        if nfl == 0 and (pspec is None or pspec.shape[-1] == 0):
+            pspec = None  # a task whose V-set owns no field: no local array, and it follows the path of the others
+        elif pspec is None or pspec.ndim != 2 or pspec.shape[1] != nfl or pspec.shape[0] != trans_inq(kresol, "nspec2"):
+            raise TransError("%s: PSPEC must have shape (nspec2, %d)" % (who, nfl))
         g = _gs_zeros((nm, ns2g), dt, gs == EMI_MEM_DEVICE, pspec) if nm else None
-        _chk(getattr(lib(), "emi_%sgath_spec_m" % _e)(kresol, gs, _gs_ptr(g, dt, who, "PSPECG"), kfgathg, _iptr(kto), ls, _gs_ptr(pspec, dt, who, "PSPEC")))
+        a = (kresol, gs, _gs_ptr(g, dt, who, "PSPECG"), kfgathg, _iptr(kto))
+        b = (ls, _gs_ptr(pspec, dt, who, "PSPEC"))
+        _chk(getattr(lib(), "emi_%sgath_spec_m" % _e)(*a, *b) if kv is None else lib().emi_gath_spec_v(*a, _iptr(kv), *b))
         return None if g is None else (g.t() if _is_torch(g) else np.ascontiguousarray(g.T))
     loc = np.ascontiguousarray(_np(pspec), dtype=dt)
     g = np.zeros((nm, ns2g), dtype=dt) if nm else None

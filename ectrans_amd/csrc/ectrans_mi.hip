@@ -4110,52 +4110,94 @@ extern "C" int emi_inq_tasks(int *nproc, int *myproc) {
   return EMI_SUCCESS;
 }
 namespace {
-struct TaskLayout {  // global <-> per-task positions of one resolution
+struct TaskLayout {  // global <-> per-task positions of one resolution, over all NPROC = NPRTRW x NPRTRV tasks (task t = w NPRTRV + v)
   std::vector<long long> iasm0g;              // [N+1] global start of wavenumber m
   std::vector<long long> mlen;                // [N+1] reals of wavenumber m: 2 (NSMAX - m + 1), or 4 (KNTMP(m) + 1) on a limited-area handle
-  std::vector<std::vector<int>> ms;           // [task] its wavenumbers, ascending
-  std::vector<std::vector<long long>> start;  // [task][i] local start of ms[task][i]
-  std::vector<long long> nspec2, gp0, ngp;    // [task]
+  std::vector<std::vector<int>> ms;           // [W-set] its wavenumbers, ascending
+  std::vector<std::vector<long long>> start;  // [W-set][i] local start of ms[W-set][i]
+  std::vector<int> wset;                      // [task] its W-set: a task's spectral layout is that of its W-set
+  std::vector<long long> nspec2, gp0, ngp;    // [task] (grid: its band, or its sub-band with V-sets)
+  int nt = 1, me = 0;                         // tasks; this task
 };
 TaskLayout task_layout(const Plan &P) {
   TaskLayout L;
-  const int N = P.nsmax, NP = P.nproc;
+  const int N = P.nsmax, NW = P.nproc, NV = P.nprv;
+  L.nt = NW * NV, L.me = P.me * NV + P.mev;
   L.iasm0g.assign(N + 2, 0);
   L.mlen.assign(N + 1, 0);
   for (int m = 0; m <= N; m++) {  // (a limited-area handle: N = KMSMAX; the global field is the one-task layout, NCPL4M(m) reals per m)
     L.mlen[m] = P.lam ? 4LL * (P.kntmp[m] + 1) : 2LL * (N - m + 1);
     L.iasm0g[m + 1] = L.iasm0g[m] + L.mlen[m];
   }
-  L.ms.assign(NP, {});
-  L.start.assign(NP, {});
-  L.nspec2.assign(NP, 0);
+  L.ms.assign(NW, {});
+  L.start.assign(NW, {});
+  std::vector<long long> wspec2(NW, 0);
   for (int m = 0; m <= N; m++) {
-    const int t = P.procm[m];
-    L.ms[t].push_back(m);
-    L.start[t].push_back(L.nspec2[t]);
-    L.nspec2[t] += L.mlen[m];
+    const int w = P.procm[m];
+    L.ms[w].push_back(m);
+    L.start[w].push_back(wspec2[w]);
+    wspec2[w] += L.mlen[m];
   }
   std::vector<long long> cum(P.ndgl + 1, 0);
   for (int j = 0; j < P.ndgl; j++) cum[j + 1] = cum[j] + P.nloen[j];
-  L.gp0.assign(NP, 0);
-  L.ngp.assign(NP, 0);
-  for (int t = 0; t < NP; t++) {
-    L.gp0[t] = cum[P.latlo[t]];
-    L.ngp[t] = cum[P.latlo[t + 1]] - cum[P.latlo[t]];
+  L.wset.assign(L.nt, 0);
+  L.nspec2.assign(L.nt, 0);
+  L.gp0.assign(L.nt, 0);
+  L.ngp.assign(L.nt, 0);
+  for (int t = 0; t < L.nt; t++) {  // latitude order = task order
+    const int w = t / NV, v = t % NV;
+    L.wset[t] = w;
+    L.nspec2[t] = wspec2[w];
+    L.gp0[t] = cum[P.vfirst(w, v)];
+    L.ngp[t] = cum[P.vlast(w, v)] - cum[P.vfirst(w, v)];
   }
   return L;
 }
+// Which task holds which field in its local array.  A grid field, and every field with NPRTRV = 1, lives on all tasks; with V-sets
+// a spectral field lives on the NPRTRW tasks of ONE V-set (KVSET of dist_spec.h / gath_spec.h): PSPEC of a task holds the fields
+// of its own V-set in ascending order, which may be none (dist_spec_control_mod.F90:96, gath_spec_control_mod.F90).
+struct FieldSets {
+  int nprv = 1;
+  std::vector<int> vs;    // [field] its V-set (0-based); -1: every task holds it
+  std::vector<int> lidx;  // [field] its position among the local fields of a task that holds it
+  bool holds(int t, int f) const { return vs[f] < 0 || vs[f] == t % nprv; }
+  int nlocal(int t) const {
+    int n = 0;
+    for (size_t f = 0; f < vs.size(); f++) n += holds(t, (int)f) ? 1 : 0;
+    return n;
+  }
+  unsigned hash() const {  // FNV-1a of the V-sets: what the tasks of a call compare
+    unsigned h = 2166136261u;
+    for (int v : vs) h = (h ^ (unsigned)(v + 1)) * 16777619u;
+    return h;
+  }
+};
+int field_sets(const Plan &P, bool spec, int nfld, const int *kvset, const char *who, FieldSets &F) {
+  F.nprv = P.nprv;
+  F.vs.assign(std::max(nfld, 0), -1);
+  F.lidx.assign(std::max(nfld, 0), 0);
+  if (spec && P.nprv > 1 && !kvset) EMI_FAIL(EMI_ERR_ARG, "%s:KVSET MISSING, NPRTRV > 1", who);
+  std::vector<int> seen(P.nprv, 0);
+  for (int f = 0; f < nfld; f++) {
+    if (spec && kvset && (kvset[f] < 1 || kvset[f] > P.nprv))  // (also with NPRTRV = 1, as gath_spec.F90:169-172)
+      EMI_FAIL(EMI_ERR_ARG, "%s:KVSET CONTAINS VALUES OUTSIDE RANGE (KVSET(%d) = %d, NPRTRV = %d)", who, f + 1, kvset[f], P.nprv);
+    if (spec && P.nprv > 1) {
+      F.vs[f] = kvset[f] - 1;
+      F.lidx[f] = seen[F.vs[f]]++;
+    } else {
+      F.lidx[f] = f;
+    }
+  }
+  return 0;
+}
 int check_tasks(const Plan &P, const int *k, int nfld, const char *who, bool host_path = true) {
-  // V-sets: a spectral field lives on the NPRTRW tasks of ONE V-set (KVSET of dist_spec.h / gath_spec.h), a grid field on the
-  // sub-bands of all NPROC tasks; these re-layout helpers know the W-set decomposition only.  Hosts with NPRTRV > 1 move their
-  // global fields themselves (TRANS_INQ gives every task's share: "latlo", "myms", "nasm0", "mysetv").
-  if (P.nprv > 1) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: not available with NPRTRV > 1", who);
+  const int NT = P.nproc * P.nprv;
   if (nfld < 0 || (nfld > 0 && !k)) EMI_FAIL(EMI_ERR_ARG, "%s: task list missing", who);
   for (int f = 0; f < nfld; f++)
-    if (k[f] < 1 || k[f] > P.nproc) EMI_FAIL(EMI_ERR_ARG, "%s: task %d of field %d outside 1..%d", who, k[f], f + 1, P.nproc);
-  if (host_path && P.nproc > 1 && (!G.hc_bcast || !G.hc_gather))
-    EMI_FAIL(EMI_ERR_STATE, "%s: %d tasks but no host collectives registered (emi_set_host_collectives)", who, P.nproc);
-  if (!host_path && P.nproc > 1 && !G.a2a) EMI_FAIL(EMI_ERR_STATE, "%s: %d tasks but no all-to-all-v hook registered (emi_set_alltoallv)", who, P.nproc);
+    if (k[f] < 1 || k[f] > NT) EMI_FAIL(EMI_ERR_ARG, "%s: task %d of field %d outside 1..%d", who, k[f], f + 1, NT);
+  if (host_path && NT > 1 && (!G.hc_bcast || !G.hc_gather))
+    EMI_FAIL(EMI_ERR_STATE, "%s: %d tasks but no host collectives registered (emi_set_host_collectives)", who, NT);
+  if (!host_path && NT > 1 && !G.a2a) EMI_FAIL(EMI_ERR_STATE, "%s: %d tasks but no all-to-all-v hook registered (emi_set_alltoallv)", who, NT);
   return 0;
 }
 int slot_of(const int *ksort, int f, int nfld, const char *who, int *slot) {
@@ -4165,54 +4207,60 @@ int slot_of(const int *ksort, int f, int nfld, const char *who, int *slot) {
 }
 }  // namespace
 
-// global fields on their source tasks -> every task's share.  One broadcast per source task.
+// global fields on their source tasks -> every task's share.  One broadcast per source task, over all tasks: a task outside the
+// V-set of a spectral field takes part and drops it.
 template <bool SPEC>
-static int dist_impl(int kresol, const void *glob, int nfld, const int *kfrom, const int *ksort, int kproma, void *loc, const char *who, bool lam = false) {
+static int dist_impl(int kresol, const void *glob, int nfld, const int *kfrom, const int *kvset, const int *ksort, int kproma, void *loc, const char *who,
+                     bool lam = false) {
   Plan *Pp = get_plan(kresol);
   if (!Pp) EMI_FAIL(EMI_ERR_STATE, "%s: unknown resolution %d", who, kresol);
   if (Pp->lam && !lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): this routine serves the spherical transforms only", who, kresol);
   if (!Pp->lam && lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is not a limited-area handle: it was not set up by ESETUP_TRANS", who, kresol);
   Plan &P = *Pp;
+  FieldSets F;
+  if (field_sets(P, SPEC, nfld, kvset, who, F)) return EMI_ERR_ARG;
   if (check_tasks(P, kfrom, nfld, who)) return EMI_ERR_ARG;
-  if (!loc) EMI_FAIL(EMI_ERR_ARG, "%s: local array missing", who);
   const TaskLayout L = task_layout(P);
+  const int me = L.me, nfl = F.nlocal(me);  // nfl: the fields of PSPEC / PGP on this task
+  if (!loc && (nfl > 0 || P.nprv == 1)) EMI_FAIL(EMI_ERR_ARG, "%s: local array missing", who);
   const size_t esz = P.esz;
   const long long nglob = SPEC ? (long long)P.nspec2g : (long long)P.ngptotg;
-  const int nproma = kproma > 0 ? kproma : P.ngptot;
+  const int nproma = kproma > 0 ? kproma : (int)L.ngp[me];
   std::vector<char> tmp;
   long long mine_done = 0;  // global fields of this task consumed so far
-  for (int root = 0; root < P.nproc; root++) {
+  for (int root = 0; root < L.nt; root++) {
     std::vector<int> fl;
     for (int f = 0; f < nfld; f++)
       if (kfrom[f] == root + 1) fl.push_back(f);
     if (fl.empty()) continue;
     const long long bytes = (long long)fl.size() * nglob * (long long)esz;
     const char *buf;
-    if (root == P.me) {
+    if (root == me) {
       if (!glob) EMI_FAIL(EMI_ERR_ARG, "%s: this task is the source of %zu fields but passes no global array", who, fl.size());
       buf = (const char *)glob + (size_t)mine_done * nglob * esz;
       mine_done += (long long)fl.size();
-      if (P.nproc > 1 && G.hc_bcast(G.hc_user, (void *)buf, bytes, root)) EMI_FAIL(EMI_ERR_RUNTIME, "%s: broadcast failed", who);
+      if (L.nt > 1 && G.hc_bcast(G.hc_user, (void *)buf, bytes, root)) EMI_FAIL(EMI_ERR_RUNTIME, "%s: broadcast failed", who);
     } else {
       tmp.resize((size_t)bytes);
       if (G.hc_bcast(G.hc_user, tmp.data(), bytes, root)) EMI_FAIL(EMI_ERR_RUNTIME, "%s: broadcast failed", who);
       buf = tmp.data();
     }
     for (size_t i = 0; i < fl.size(); i++) {
-      int slot;
-      if (slot_of(ksort, fl[i], nfld, who, &slot)) return EMI_ERR_ARG;
+      if (!F.holds(me, fl[i])) continue;
+      int slot;  // KSORT is indexed by the local field (dist_spec_control_mod.F90:255, 288)
+      if (slot_of(ksort, F.lidx[fl[i]], nfl, who, &slot)) return EMI_ERR_ARG;
       const char *g = buf + i * (size_t)nglob * esz;
-      if (SPEC) {  // PSPEC(nfld, nspec2): element (slot, isp)
-        const std::vector<int> &ms = L.ms[P.me];
+      if (SPEC) {  // PSPEC(nfl, nspec2): element (slot, isp)
+        const std::vector<int> &ms = L.ms[L.wset[me]];
         for (size_t k = 0; k < ms.size(); k++) {
-          const long long cnt = L.mlen[ms[k]], gs = L.iasm0g[ms[k]], ls = L.start[P.me][k];
-          for (long long e = 0; e < cnt; e++) memcpy((char *)loc + ((size_t)(ls + e) * nfld + slot) * esz, g + (size_t)(gs + e) * esz, esz);
+          const long long cnt = L.mlen[ms[k]], gs = L.iasm0g[ms[k]], ls = L.start[L.wset[me]][k];
+          for (long long e = 0; e < cnt; e++) memcpy((char *)loc + ((size_t)(ls + e) * nfl + slot) * esz, g + (size_t)(gs + e) * esz, esz);
         }
-      } else {  // PGP(nproma, nfld, ngpblks): point p -> block p / nproma
-        const long long g0 = L.gp0[P.me], ng = L.ngp[P.me];
+      } else {  // PGP(nproma, nfl, ngpblks): point p -> block p / nproma
+        const long long g0 = L.gp0[me], ng = L.ngp[me];
         for (long long p0 = 0; p0 < ng; p0 += nproma) {
           const long long w = std::min<long long>(nproma, ng - p0), blk = p0 / nproma;
-          memcpy((char *)loc + ((size_t)(blk * nfld + slot) * nproma) * esz, g + (size_t)(g0 + p0) * esz, (size_t)w * esz);
+          memcpy((char *)loc + ((size_t)(blk * nfl + slot) * nproma) * esz, g + (size_t)(g0 + p0) * esz, (size_t)w * esz);
         }
       }
     }
@@ -4220,19 +4268,23 @@ static int dist_impl(int kresol, const void *glob, int nfld, const int *kfrom, c
   return EMI_SUCCESS;
 }
 
-// every task's share -> global fields on their target tasks.  An all-gather-v of the packed local fields per chunk of fields.
+// every task's share -> global fields on their target tasks.  An all-gather-v of the packed local fields per chunk of fields: a task
+// sends the fields of the chunk that it holds (with V-sets a spectral field comes from the tasks of its V-set only).
 template <bool SPEC>
-static int gath_impl(int kresol, void *glob, int nfld, const int *kto, int kproma, const void *loc, const char *who, bool lam = false) {
+static int gath_impl(int kresol, void *glob, int nfld, const int *kto, const int *kvset, int kproma, const void *loc, const char *who, bool lam = false) {
   Plan *Pp = get_plan(kresol);
   if (!Pp) EMI_FAIL(EMI_ERR_STATE, "%s: unknown resolution %d", who, kresol);
   if (Pp->lam && !lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is a limited-area handle (ESETUP_TRANS): this routine serves the spherical transforms only", who, kresol);
   if (!Pp->lam && lam) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: resolution %d is not a limited-area handle: it was not set up by ESETUP_TRANS", who, kresol);
   Plan &P = *Pp;
+  FieldSets F;
+  if (field_sets(P, SPEC, nfld, kvset, who, F)) return EMI_ERR_ARG;
   if (check_tasks(P, kto, nfld, who)) return EMI_ERR_ARG;
-  if (!loc) EMI_FAIL(EMI_ERR_ARG, "%s: local array missing", who);
   const TaskLayout L = task_layout(P);
+  const int NT = L.nt, me = L.me, nfl = F.nlocal(me);
+  if (!loc && (nfl > 0 || P.nprv == 1)) EMI_FAIL(EMI_ERR_ARG, "%s: local array missing", who);
   const size_t esz = P.esz;
-  const int NP = P.nproc, nproma = kproma > 0 ? kproma : P.ngptot;
+  const int nproma = kproma > 0 ? kproma : (int)L.ngp[me];
   const long long nglob = SPEC ? (long long)P.nspec2g : (long long)P.ngptotg;
   auto nloc = [&](int t) { return SPEC ? L.nspec2[t] : L.ngp[t]; };
   // Fields in chunks whose gathered image stays below 256 MiB: every task receives every field of a chunk whatever KTO says (the
@@ -4242,49 +4294,58 @@ static int gath_impl(int kresol, void *glob, int nfld, const int *kto, int kprom
   const int chunk = (int)std::max<long long>(1, std::min<long long>(nfld, budget / std::max<long long>(per_field, 1)));
   long long i_mine = 0;
   std::vector<char> mine, all;
-  std::vector<long long> cnt(NP), dsp(NP);
+  std::vector<long long> cnt(NT), dsp(NT);
+  std::vector<int> held(NT);  // fields of the chunk that task t holds
   for (int fa = 0; fa < nfld; fa += chunk) {
     const int nf = std::min(chunk, nfld - fa);
-    // pack [field][local element]
-    mine.resize((size_t)nf * nloc(P.me) * esz);
-    for (int fc = 0; fc < nf; fc++) {
-      const int f = fa + fc;
-      char *dst = mine.data() + (size_t)fc * nloc(P.me) * esz;
+    for (int t = 0; t < NT; t++) {
+      held[t] = 0;
+      for (int f = fa; f < fa + nf; f++) held[t] += F.holds(t, f) ? 1 : 0;
+    }
+    // pack [held field][local element]
+    mine.resize((size_t)held[me] * nloc(me) * esz);
+    for (int f = fa, fc = 0; f < fa + nf; f++) {
+      if (!F.holds(me, f)) continue;
+      const int lf = F.lidx[f];
+      char *dst = mine.data() + (size_t)fc++ * nloc(me) * esz;
       if (SPEC) {
-        for (long long e = 0; e < nloc(P.me); e++) memcpy(dst + (size_t)e * esz, (const char *)loc + ((size_t)e * nfld + f) * esz, esz);
+        for (long long e = 0; e < nloc(me); e++) memcpy(dst + (size_t)e * esz, (const char *)loc + ((size_t)e * nfl + lf) * esz, esz);
       } else {
-        for (long long p0 = 0; p0 < nloc(P.me); p0 += nproma) {
-          const long long w = std::min<long long>(nproma, nloc(P.me) - p0), blk = p0 / nproma;
-          memcpy(dst + (size_t)p0 * esz, (const char *)loc + ((size_t)(blk * nfld + f) * nproma) * esz, (size_t)w * esz);
+        for (long long p0 = 0; p0 < nloc(me); p0 += nproma) {
+          const long long w = std::min<long long>(nproma, nloc(me) - p0), blk = p0 / nproma;
+          memcpy(dst + (size_t)p0 * esz, (const char *)loc + ((size_t)(blk * nfl + lf) * nproma) * esz, (size_t)w * esz);
         }
       }
     }
     const char *base = mine.data();
-    if (NP > 1) {
+    if (NT > 1) {
       long long tot = 0;
-      for (int t = 0; t < NP; t++) {
-        cnt[t] = (long long)nf * nloc(t) * (long long)esz;
+      for (int t = 0; t < NT; t++) {
+        cnt[t] = (long long)held[t] * nloc(t) * (long long)esz;
         dsp[t] = tot;
         tot += cnt[t];
       }
       all.resize((size_t)tot);
-      if (G.hc_gather(G.hc_user, mine.data(), cnt[P.me], all.data(), cnt.data(), dsp.data(), NP)) EMI_FAIL(EMI_ERR_RUNTIME, "%s: all-gather-v failed", who);
+      if (G.hc_gather(G.hc_user, mine.data(), cnt[me], all.data(), cnt.data(), dsp.data(), NT)) EMI_FAIL(EMI_ERR_RUNTIME, "%s: all-gather-v failed", who);
       base = all.data();
     } else {
       dsp[0] = 0;
     }
-    for (int fc = 0; fc < nf; fc++) {
-      const int f = fa + fc;
-      if (kto[f] != P.me + 1) continue;
+    for (int f = fa; f < fa + nf; f++) {
+      if (kto[f] != me + 1) continue;
       if (!glob) EMI_FAIL(EMI_ERR_ARG, "%s: this task is the target of field %d but passes no global array", who, f + 1);
       char *g = (char *)glob + (size_t)i_mine * nglob * esz;
       i_mine++;
-      for (int t = 0; t < NP; t++) {
+      for (int t = 0; t < NT; t++) {
+        if (!F.holds(t, f)) continue;
+        int fc = 0;  // position of field f in the block of task t
+        for (int h = fa; h < f; h++) fc += F.holds(t, h) ? 1 : 0;
         const char *src = base + dsp[t] + (size_t)fc * nloc(t) * esz;
         if (SPEC) {
-          for (size_t k = 0; k < L.ms[t].size(); k++) {
-            const long long cnte = L.mlen[L.ms[t][k]];
-            memcpy(g + (size_t)L.iasm0g[L.ms[t][k]] * esz, src + (size_t)L.start[t][k] * esz, (size_t)cnte * esz);
+          const int w = L.wset[t];
+          for (size_t k = 0; k < L.ms[w].size(); k++) {
+            const long long cnte = L.mlen[L.ms[w][k]];
+            memcpy(g + (size_t)L.iasm0g[L.ms[w][k]] * esz, src + (size_t)L.start[w][k] * esz, (size_t)cnte * esz);
           }
         } else {
           memcpy(g + (size_t)L.gp0[t] * esz, src, (size_t)L.ngp[t] * esz);
@@ -4296,31 +4357,31 @@ static int gath_impl(int kresol, void *glob, int nfld, const int *kto, int kprom
 }
 
 extern "C" int emi_dist_spec(int kresol, const void *specg, int nfld, const int *kfrom, const int *ksort, void *spec) {
-  return dist_impl<true>(kresol, specg, nfld, kfrom, ksort, 0, spec, "DIST_SPEC");
+  return dist_impl<true>(kresol, specg, nfld, kfrom, nullptr, ksort, 0, spec, "DIST_SPEC");
 }
 extern "C" int emi_gath_spec(int kresol, void *specg, int nfld, const int *kto, const void *spec) {
-  return gath_impl<true>(kresol, specg, nfld, kto, 0, spec, "GATH_SPEC");
+  return gath_impl<true>(kresol, specg, nfld, kto, nullptr, 0, spec, "GATH_SPEC");
 }
 extern "C" int emi_dist_grid(int kresol, const void *gpg, int nfld, const int *kfrom, const int *ksort, int kproma, void *gp) {
-  return dist_impl<false>(kresol, gpg, nfld, kfrom, ksort, kproma, gp, "DIST_GRID");
+  return dist_impl<false>(kresol, gpg, nfld, kfrom, nullptr, ksort, kproma, gp, "DIST_GRID");
 }
 extern "C" int emi_gath_grid(int kresol, void *gpg, int nfld, const int *kto, int kproma, const void *gp) {
-  return gath_impl<false>(kresol, gpg, nfld, kto, kproma, gp, "GATH_GRID");
+  return gath_impl<false>(kresol, gpg, nfld, kto, nullptr, kproma, gp, "GATH_GRID");
 }
 // EDIST_SPEC / EGATH_SPEC / EDIST_GRID / EGATH_GRID: the same on a limited-area handle.  A global spectral field is the one-task layout,
 // m = 0 .. KMSMAX ascending with 4 (KNTMP(m) + 1) reals each (gath_spec_control_mod.F90:108-113 with KN = NCPL4M); a global grid field
 // the NDGL x NDLON points row after row, the tasks' bands of whole rows in task order.
 extern "C" int emi_edist_spec(int kresol, const void *specg, int nfld, const int *kfrom, const int *ksort, void *spec) {
-  return dist_impl<true>(kresol, specg, nfld, kfrom, ksort, 0, spec, "EDIST_SPEC", true);
+  return dist_impl<true>(kresol, specg, nfld, kfrom, nullptr, ksort, 0, spec, "EDIST_SPEC", true);
 }
 extern "C" int emi_egath_spec(int kresol, void *specg, int nfld, const int *kto, const void *spec) {
-  return gath_impl<true>(kresol, specg, nfld, kto, 0, spec, "EGATH_SPEC", true);
+  return gath_impl<true>(kresol, specg, nfld, kto, nullptr, 0, spec, "EGATH_SPEC", true);
 }
 extern "C" int emi_edist_grid(int kresol, const void *gpg, int nfld, const int *kfrom, const int *ksort, int kproma, void *gp) {
-  return dist_impl<false>(kresol, gpg, nfld, kfrom, ksort, kproma, gp, "EDIST_GRID", true);
+  return dist_impl<false>(kresol, gpg, nfld, kfrom, nullptr, ksort, kproma, gp, "EDIST_GRID", true);
 }
 extern "C" int emi_egath_grid(int kresol, void *gpg, int nfld, const int *kto, int kproma, const void *gp) {
-  return gath_impl<false>(kresol, gpg, nfld, kto, kproma, gp, "EGATH_GRID", true);
+  return gath_impl<false>(kresol, gpg, nfld, kto, nullptr, kproma, gp, "EGATH_GRID", true);
 }
 
 // CRC-64/ECMA-182, table driven (ectrans-benchmark.F90:1455-1600 calls fiat's crc64, un-vendored)
@@ -4566,6 +4627,8 @@ static int agree_on_mixed_arrays(const char *who, int ndev, int nhost) {
 // unpacked by k_spec_fields (PSPEC is field-fastest) or k_gridcopy (PGP is NPROMA-blocked); the global side by k_run_copy over
 // the runs of TaskLayout, straight into / out of the caller's global array where that lives in device memory, else through a
 // staged image and one copy per chunk.
+// V-sets (NPRTRV > 1): the tasks are all NPROC = NPRTRW x NPRTRV, a grid field lives on every task's sub-band, a spectral field on the
+// NPRTRW tasks of its V-set only (FieldSets): a block holds the fields that travel between the two tasks AND that the local side holds.
 // ------------------------------------------------------------------------------------------
 static int gs_run_copy(Plan &P, const void *src, void *dst, std::vector<CopyRun> &runs, int nf, std::vector<StageBuf *> &keep, emi_stream_t st) {
   if (runs.empty() || nf == 0) return 0;
@@ -4605,67 +4668,89 @@ static int gs_local(Plan &P, void *loc, void *wire, const std::vector<int> &slot
   }
   return to_wire ? v_copy(P, arr, blk, 0, 0, nloc, nproma, nloc, keep, st) : v_copy(P, blk, arr, 0, 0, nloc, nloc, nproma, keep, st);
 }
-// gath: every task's share -> global fields on their targets; else global fields on their sources -> every task's share
+// gath: every task's share -> global fields on their targets; else global fields on their sources -> every task's share.
+// nfld counts the GLOBAL fields; the local array holds the F.nlocal(me) of them that live on this task (FieldSets).
 template <bool SPEC>
-static int gs_device(Plan &P, bool gath, void *glob, bool glob_dev, int nfld, const int *ktask, const int *ksort, int kproma, void *loc, const char *who) {
+static int gs_device(Plan &P, bool gath, void *glob, bool glob_dev, int nfld, const int *ktask, const FieldSets &F, const int *ksort, int kproma, void *loc,
+                     const char *who) {
   const TaskLayout L = task_layout(P);
-  const int esz = P.esz, NP = P.nproc, me = P.me, nproma = kproma > 0 ? kproma : P.ngptot;
+  const int esz = P.esz, NT = L.nt, me = L.me, nfl = F.nlocal(me), nproma = kproma > 0 ? kproma : (int)L.ngp[me];
   const long long nglob = SPEC ? (long long)P.nspec2g : (long long)P.ngptotg;
   auto nloc = [&](int t) { return SPEC ? L.nspec2[t] : L.ngp[t]; };
   std::vector<int> slot(nfld);
-  for (int f = 0; f < nfld; f++)  // (KSORT and the presence of the global array: checked by gs_local_args before the tasks compared)
-    slot[f] = (gath || !ksort) ? f : ksort[f] - 1;
+  for (int f = 0; f < nfld; f++)  // (KSORT and the presence of the arrays: checked by gs_local_args before the tasks compared)
+    slot[f] = (gath || !ksort || !F.holds(me, f)) ? F.lidx[f] : ksort[F.lidx[f]] - 1;
   // the chunk rule of the host path, the same on every task: the global image of a chunk stays below 256 MiB / EMI_GATH_CHUNK
   const long long per_field = nglob * (long long)esz;
   const long long budget = (getenv("EMI_GATH_CHUNK") && *getenv("EMI_GATH_CHUNK")) ? atoll(getenv("EMI_GATH_CHUNK")) : (256LL << 20);
   const int chunk = (int)std::max<long long>(1, std::min<long long>(nfld, budget / std::max<long long>(per_field, 1)));
+  // V-sets: the fields of mine that a peer holds are not evenly spaced in the global image, so every (field, run) is a run of its own
+  const bool run_per_field = SPEC && P.nprv > 1;
   const emi_stream_t st = (emi_stream_t)0;
   if (plan_begin(P, st)) return EMI_ERR_RUNTIME;  // behind the last transform of the handle
   g_pt.begin(G.profile != 0, G.profile == 2);
-  std::vector<long long> before(NP + 1, 0);  // elements of the tasks below t
-  for (int t = 0; t < NP; t++) before[t + 1] = before[t] + nloc(t);
   long long i_mine = 0;
   int rc = EMI_SUCCESS;
   for (int fa = 0; fa < nfld && rc == EMI_SUCCESS; fa += chunk) {
     const int nf = std::min(chunk, nfld - fa);
-    std::vector<int> order, cnt(NP, 0);  // the fields of the chunk by (peer, field); fields per peer
-    for (int t = 0; t < NP; t++)
+    // the fields of the chunk that this task holds, by (peer, field); cnt: of them per peer; minef: the global fields of mine;
+    // held[t]: of those, the ones task t holds
+    std::vector<int> order, cnt(NT, 0), minef, held(NT, 0);
+    for (int t = 0; t < NT; t++)
       for (int f = fa; f < fa + nf; f++)
-        if (ktask[f] == t + 1) order.push_back(f), cnt[t]++;
-    const int nmine = cnt[me];
+        if (ktask[f] == t + 1 && F.holds(me, f)) order.push_back(f), cnt[t]++;
+    for (int f = fa; f < fa + nf; f++)
+      if (ktask[f] == me + 1) minef.push_back(f);
+    const int nmine = (int)minef.size(), nord = (int)order.size();
+    std::vector<long long> boff(NT + 1, 0);  // elements of the global-side blocks of the tasks below t
+    for (int t = 0; t < NT; t++) {
+      for (int f : minef) held[t] += F.holds(t, f) ? 1 : 0;
+      boff[t + 1] = boff[t] + (long long)held[t] * nloc(t);
+    }
     std::vector<int> wslots;
     for (int f : order) wslots.push_back(slot[f]);
-    // locb: the dense fields [w][nloc(me)] of the local side; globb: the blocks [task][field of mine][nloc(task)] of the global side
-    const size_t locbytes = (size_t)nf * nloc(me) * esz, globbytes = (size_t)nmine * nglob * esz;
-    StageBuf locb(locbytes), globb(NP > 1 ? globbytes : 0), img(glob_dev ? 0 : globbytes);
-    if ((locbytes && !locb.p) || (NP > 1 && globbytes && !globb.p) || (!glob_dev && globbytes && !img.p))
+    // locb: the dense fields [w][nloc(me)] of the local side; globb: the blocks [task][field of mine it holds][nloc(task)] of the global side
+    const size_t locbytes = (size_t)nord * nloc(me) * esz, globbytes = (size_t)nmine * nglob * esz, blkbytes = (size_t)boff[NT] * esz;
+    StageBuf locb(locbytes), globb(NT > 1 ? blkbytes : 0), img(glob_dev ? 0 : globbytes);
+    if ((locbytes && !locb.p) || (NT > 1 && blkbytes && !globb.p) || (!glob_dev && globbytes && !img.p))
       EMI_FAIL(EMI_ERR_RUNTIME, "%s: no device memory for the exchange buffers of %d fields", who, nf);
-    void *gb = NP > 1 ? globb.p : locb.p;  // one task: the two sides are one buffer, [field][nglob]
+    void *gb = NT > 1 ? globb.p : locb.p;  // one task: the two sides are one buffer, [field][nglob]
     char *gcall = glob ? (char *)glob + (size_t)i_mine * nglob * esz : nullptr;
     void *gimg = glob_dev ? (void *)gcall : img.p;
     std::vector<StageBuf *> keep;
     std::vector<CopyRun> runs;
-    for (int t = 0; t < NP && nmine; t++) {  // (global position, position in the block of task t) of every run
-      const long long boff = (long long)nmine * before[t];
-      if (SPEC) {
-        for (size_t k = 0; k < L.ms[t].size(); k++) {
-          const int m = L.ms[t][k];
-          if (L.mlen[m] > 0) runs.push_back(CopyRun{L.iasm0g[m], boff + L.start[t][k], nglob, nloc(t), (int)L.mlen[m], 0});
+    for (int t = 0; t < NT && nmine; t++) {  // (global position, position in the block of task t) of every run
+      if (!held[t]) continue;
+      const int w = L.wset[t];
+      if (run_per_field) {
+        for (int j = 0, jt = 0; j < nmine; j++) {
+          if (!F.holds(t, minef[j])) continue;
+          for (size_t k = 0; k < L.ms[w].size(); k++) {
+            const int m = L.ms[w][k];
+            if (L.mlen[m] > 0) runs.push_back(CopyRun{(long long)j * nglob + L.iasm0g[m], boff[t] + (long long)jt * nloc(t) + L.start[w][k], nglob, nloc(t), (int)L.mlen[m], 0});
+          }
+          jt++;
+        }
+      } else if (SPEC) {
+        for (size_t k = 0; k < L.ms[w].size(); k++) {
+          const int m = L.ms[w][k];
+          if (L.mlen[m] > 0) runs.push_back(CopyRun{L.iasm0g[m], boff[t] + L.start[w][k], nglob, nloc(t), (int)L.mlen[m], 0});
         }
       } else if (L.ngp[t] > 0) {
-        runs.push_back(CopyRun{L.gp0[t], boff, nglob, nloc(t), (int)L.ngp[t], 0});
+        runs.push_back(CopyRun{L.gp0[t], boff[t], nglob, nloc(t), (int)L.ngp[t], 0});
       }
     }
-    std::vector<long long> cl(NP), cg(NP);  // bytes of the local-side and the global-side block with every task
-    for (int t = 0; t < NP; t++) cl[t] = (long long)cnt[t] * nloc(me) * esz, cg[t] = (long long)nmine * nloc(t) * esz;
+    const int nrf = run_per_field ? 1 : nmine;  // fields that every run stands for
+    std::vector<long long> cl(NT), cg(NT);  // bytes of the local-side and the global-side block with every task
+    for (int t = 0; t < NT; t++) cl[t] = (long long)cnt[t] * nloc(me) * esz, cg[t] = (long long)held[t] * nloc(t) * esz;
     bool bad;
     if (gath) {
-      bad = gs_local<SPEC>(P, loc, locb.p, wslots, nfld, nloc(me), nproma, true, keep, st) || (NP > 1 && hook_alltoallv(locb.p, cl, gb, cg, NP, P.nprv, P.mev, st));
+      bad = gs_local<SPEC>(P, loc, locb.p, wslots, nfl, nloc(me), nproma, true, keep, st) || (NT > 1 && hook_alltoallv(locb.p, cl, gb, cg, NT, 1, 0, st));
       for (CopyRun &r : runs) std::swap(r.src0, r.dst0), std::swap(r.sfs, r.dfs);
-      bad = bad || gs_run_copy(P, gb, gimg, runs, nmine, keep, st) || (!glob_dev && globbytes && emi_d2h(gcall, gimg, globbytes, st));
+      bad = bad || gs_run_copy(P, gb, gimg, runs, nrf, keep, st) || (!glob_dev && globbytes && emi_d2h(gcall, gimg, globbytes, st));
     } else {
-      bad = (!glob_dev && globbytes && emi_h2d(gimg, gcall, globbytes, st)) || gs_run_copy(P, gimg, gb, runs, nmine, keep, st) ||
-            (NP > 1 && hook_alltoallv(gb, cg, locb.p, cl, NP, P.nprv, P.mev, st)) || gs_local<SPEC>(P, loc, locb.p, wslots, nfld, nloc(me), nproma, false, keep, st);
+      bad = (!glob_dev && globbytes && emi_h2d(gimg, gcall, globbytes, st)) || gs_run_copy(P, gimg, gb, runs, nrf, keep, st) ||
+            (NT > 1 && hook_alltoallv(gb, cg, locb.p, cl, NT, 1, 0, st)) || gs_local<SPEC>(P, loc, locb.p, wslots, nfl, nloc(me), nproma, false, keep, st);
     }
     if (emi_stream_sync(st) && !bad) {  // the call waits for its stream: the buffers go back to the pool, the caller needs no emi_wait
       emi_set_error("%s: the kernels or copies of the call did not complete", who);
@@ -4689,75 +4774,117 @@ static int gs_handle(int kresol, const char *who, bool lam, Plan **out) {
 // compare (one word each) and fail together; without them it is the caller's duty, as for EMI_MEM_AUTO of the transforms.
 // What one task alone can find wrong with the arguments of a device-path call, found BEFORE the tasks compare: a task that returned on its own
 // would leave its peers waiting in the exchange.  The message stays in the error text of this task.
-static int gs_local_args(const Plan &P, bool gath, const void *glob, int nfld, const int *ktask, const int *ksort, const void *loc, const char *who) {
-  if (check_tasks(P, ktask, nfld, who, false)) return EMI_ERR_ARG;
-  if (!loc) EMI_FAIL(EMI_ERR_ARG, "%s: local array missing", who);
+static int gs_local_args(const Plan &P, bool gath, const void *glob, int nfld, const int *ktask, const FieldSets &F, const int *ksort, const void *loc, bool host_path,
+                         const char *who) {
+  if (check_tasks(P, ktask, nfld, who, host_path)) return EMI_ERR_ARG;
+  const int me = P.me * P.nprv + P.mev, nfl = F.nlocal(me);
+  if (!loc && (nfl > 0 || P.nprv == 1)) EMI_FAIL(EMI_ERR_ARG, "%s: local array missing", who);
   int n_glob = 0, slot;
   for (int f = 0; f < nfld; f++) {
-    if (!gath && slot_of(ksort, f, nfld, who, &slot)) return EMI_ERR_ARG;
-    if (ktask[f] == P.me + 1) n_glob++;
+    if (!gath && F.holds(me, f) && slot_of(ksort, F.lidx[f], nfl, who, &slot)) return EMI_ERR_ARG;
+    if (ktask[f] == me + 1) n_glob++;
   }
   if (n_glob && !glob)
     EMI_FAIL(EMI_ERR_ARG, gath ? "%s: this task is the target of %d fields but passes no global array" : "%s: this task is the source of %d fields but passes no global array", who, n_glob);
   return 0;
 }
-// mine: 0 host path, 1 device path, 2 a device global array beside a host local array, 3 arguments refused on this task (gs_local_args)
-static int gs_agree_on_path(const char *who, int mine) {
-  std::vector<int> all(1, mine);
+// mine: 0 host path, 1 device path, 2 a device global array beside a host local array, 3 arguments refused on this task (gs_local_args),
+// 4 no local field on this task (a V-set that owns none of the fields): it follows the others.  kvhash: FieldSets::hash, the V-sets of
+// the fields as this task names them -- tasks that disagreed on KVSET would wait for blocks that nobody sends.  *path: the agreed path.
+static int gs_agree_on_path(const char *who, int mine, unsigned kvhash, int *path) {
+  const int word[2] = {mine, (int)kvhash};
+  std::vector<int> all(word, word + 2);
   if (G.nproc_all > 1 && G.hc_gather) {
     const int NA = G.nproc_all;
-    all.assign(NA, 0);
-    std::vector<long long> cnt(NA, 4), dsp(NA);
-    for (int r = 0; r < NA; r++) dsp[r] = 4LL * r;
-    if (G.hc_gather(G.hc_user, &mine, 4, all.data(), cnt.data(), dsp.data(), NA)) EMI_FAIL(EMI_ERR_RUNTIME, "%s: all-gather-v failed", who);
+    all.assign(2 * (size_t)NA, 0);
+    std::vector<long long> cnt(NA, 8), dsp(NA);
+    for (int r = 0; r < NA; r++) dsp[r] = 8LL * r;
+    if (G.hc_gather(G.hc_user, word, 8, all.data(), cnt.data(), dsp.data(), NA)) EMI_FAIL(EMI_ERR_RUNTIME, "%s: all-gather-v failed", who);
   }
+  const size_t n = all.size() / 2;
   if (mine == 3) return EMI_ERR_ARG;  // (with this task's own message)
-  for (size_t r = 0; r < all.size(); r++)
-    if (all[r] == 3) EMI_FAIL(EMI_ERR_ARG, "%s: TASK %d REFUSED ITS ARGUMENTS (its error text says why); no task of the call went on", who, (int)r + 1);
-  for (size_t r = 0; r < all.size(); r++)
-    if (all[r] == 2)
+  for (size_t r = 0; r < n; r++)
+    if (all[2 * r] == 3) EMI_FAIL(EMI_ERR_ARG, "%s: TASK %d REFUSED ITS ARGUMENTS (its error text says why); no task of the call went on", who, (int)r + 1);
+  for (size_t r = 0; r < n; r++)
+    if (all[2 * r + 1] != word[1]) EMI_FAIL(EMI_ERR_ARG, "%s: KVSET DIFFERS BETWEEN TASKS (here and on task %d); no task of the call went on", who, (int)r + 1);
+  for (size_t r = 0; r < n; r++)
+    if (all[2 * r] == 2)
       EMI_FAIL(EMI_ERR_ARG, "%s: THE GLOBAL ARRAY IS IN DEVICE MEMORY AND THE LOCAL ARRAY IN HOST MEMORY ON TASK %d (a host local array takes the host path)", who,
-               all.size() > 1 ? (int)r + 1 : G.myproc_all);
-  for (size_t r = 0; r < all.size(); r++)
-    if (all[r] != mine)
+               n > 1 ? (int)r + 1 : G.myproc_all);
+  *path = -1;
+  for (size_t r = 0; r < n; r++) {
+    if (all[2 * r] == 4) continue;
+    if (*path < 0) *path = all[2 * r];
+    if (mine != 4 && all[2 * r] != mine)
       EMI_FAIL(EMI_ERR_ARG, "%s: THE LOCAL ARRAY IS IN %s MEMORY HERE AND IN %s MEMORY ON TASK %d (every task of a call must take the same path)", who,
                mine ? "DEVICE" : "HOST", mine ? "HOST" : "DEVICE", (int)r + 1);
+    if (mine == 4 && all[2 * r] != *path)
+      EMI_FAIL(EMI_ERR_ARG, "%s: THE LOCAL ARRAY IS IN HOST MEMORY ON SOME TASKS AND IN DEVICE MEMORY ON OTHERS, AS ON TASK %d (every task of a call must take the same path)",
+               who, (int)r + 1);
+  }
   return 0;
 }
 template <bool SPEC>
-static int gs_m(bool gath, int kresol, int glob_space, const void *glob, int nfld, const int *ktask, const int *ksort, int kproma, int loc_space, const void *loc,
-                const char *who, bool lam) {
+static int gs_m(bool gath, int kresol, int glob_space, const void *glob, int nfld, const int *ktask, const int *kvset, const int *ksort, int kproma, int loc_space,
+                const void *loc, const char *who, bool lam) {
   Plan *Pp;
   if (int rc = gs_handle(kresol, who, lam, &Pp)) return rc;
   for (int sp : {glob_space, loc_space})
     if (sp != EMI_MEM_HOST && sp != EMI_MEM_DEVICE && sp != EMI_MEM_AUTO)
       EMI_FAIL(EMI_ERR_ARG, "%s: memory space %d (EMI_MEM_HOST, EMI_MEM_DEVICE or EMI_MEM_AUTO)", who, sp);
+  if (lam && kvset) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: KVSET: V-sets are not available on a limited-area handle", who);
   if (glob_space == EMI_MEM_AUTO) glob_space = emi_ptr_space(glob);
   if (loc_space == EMI_MEM_AUTO) loc_space = emi_ptr_space(loc);
   const bool glob_dev = glob && glob_space == EMI_MEM_DEVICE, loc_dev = loc_space == EMI_MEM_DEVICE;
-  if (Pp->nprv > 1) EMI_FAIL(EMI_ERR_UNSUPPORTED, "%s: not available with NPRTRV > 1", who);
-  const int word = (!loc_dev && glob_dev) ? 2 : !loc_dev ? 0 : gs_local_args(*Pp, gath, glob, nfld, ktask, ksort, loc, who) ? 3 : 1;
-  if (gs_agree_on_path(who, word)) return EMI_ERR_ARG;
-  if (!loc_dev)
-    return gath ? gath_impl<SPEC>(kresol, (void *)glob, nfld, ktask, kproma, loc, who, lam) : dist_impl<SPEC>(kresol, glob, nfld, ktask, ksort, kproma, (void *)loc, who, lam);
-  return gs_device<SPEC>(*Pp, gath, (void *)glob, glob_dev, nfld, ktask, ksort, kproma, (void *)loc, who);
+  const Plan &P = *Pp;
+  // With V-sets the arguments are looked at on both paths before the tasks compare (a task of another V-set sees nothing wrong with
+  // a field it does not hold); with NPRTRV = 1 the host path finds its own errors, as it always did.
+  FieldSets F;
+  int word;
+  if (field_sets(P, SPEC, nfld, kvset, who, F))
+    word = 3;
+  else if (P.nprv > 1 && F.nlocal(P.me * P.nprv + P.mev) == 0 && !gs_local_args(P, gath, glob, nfld, ktask, F, ksort, loc, !loc_dev, who))
+    word = 4;
+  else if (!loc_dev && glob_dev)
+    word = 2;
+  else if (!loc_dev)
+    word = (P.nprv > 1 && gs_local_args(P, gath, glob, nfld, ktask, F, ksort, loc, true, who)) ? 3 : 0;
+  else
+    word = gs_local_args(P, gath, glob, nfld, ktask, F, ksort, loc, false, who) ? 3 : 1;
+  int path = 0;
+  if (gs_agree_on_path(who, word, F.hash(), &path)) return EMI_ERR_ARG;
+  if (path < 0) path = loc_dev ? 1 : 0;  // (no task holds a field: nothing moves)
+  if (word == 4 && path == 0 && glob_dev) EMI_FAIL(EMI_ERR_ARG, "%s: THE GLOBAL ARRAY IS IN DEVICE MEMORY AND THE CALL TAKES THE HOST PATH", who);
+  if (path == 0)
+    return gath ? gath_impl<SPEC>(kresol, (void *)glob, nfld, ktask, kvset, kproma, loc, who, lam)
+                : dist_impl<SPEC>(kresol, glob, nfld, ktask, kvset, ksort, kproma, (void *)loc, who, lam);
+  return gs_device<SPEC>(*Pp, gath, (void *)glob, glob_dev, nfld, ktask, F, ksort, kproma, (void *)loc, who);
 }
 #define EMI_GS_M(pre, PRE, lam)                                                                                                                                          \
   extern "C" int emi_##pre##dist_spec_m(int kresol, int glob_space, const void *specg, int nfld, const int *kfrom, const int *ksort, int loc_space, void *spec) {          \
-    return gs_m<true>(false, kresol, glob_space, specg, nfld, kfrom, ksort, 0, loc_space, spec, PRE "DIST_SPEC", lam);                                                    \
+    return gs_m<true>(false, kresol, glob_space, specg, nfld, kfrom, nullptr, ksort, 0, loc_space, spec, PRE "DIST_SPEC", lam);                                                    \
   }                                                                                                                                                                        \
   extern "C" int emi_##pre##gath_spec_m(int kresol, int glob_space, void *specg, int nfld, const int *kto, int loc_space, const void *spec) {                             \
-    return gs_m<true>(true, kresol, glob_space, specg, nfld, kto, nullptr, 0, loc_space, spec, PRE "GATH_SPEC", lam);                                                     \
+    return gs_m<true>(true, kresol, glob_space, specg, nfld, kto, nullptr, nullptr, 0, loc_space, spec, PRE "GATH_SPEC", lam);                                                    \
   }                                                                                                                                                                        \
   extern "C" int emi_##pre##dist_grid_m(int kresol, int glob_space, const void *gpg, int nfld, const int *kfrom, const int *ksort, int kproma, int loc_space, void *gp) { \
-    return gs_m<false>(false, kresol, glob_space, gpg, nfld, kfrom, ksort, kproma, loc_space, gp, PRE "DIST_GRID", lam);                                                  \
+    return gs_m<false>(false, kresol, glob_space, gpg, nfld, kfrom, nullptr, ksort, kproma, loc_space, gp, PRE "DIST_GRID", lam);                                                  \
   }                                                                                                                                                                        \
   extern "C" int emi_##pre##gath_grid_m(int kresol, int glob_space, void *gpg, int nfld, const int *kto, int kproma, int loc_space, const void *gp) {                     \
-    return gs_m<false>(true, kresol, glob_space, gpg, nfld, kto, nullptr, kproma, loc_space, gp, PRE "GATH_GRID", lam);                                                   \
+    return gs_m<false>(true, kresol, glob_space, gpg, nfld, kto, nullptr, nullptr, kproma, loc_space, gp, PRE "GATH_GRID", lam);                                                  \
   }
 EMI_GS_M(, "", false)
 EMI_GS_M(e, "E", true)
 #undef EMI_GS_M
+// DIST_SPEC / GATH_SPEC with KVSET (dist_spec.h, gath_spec.h): the _m forms with the V-set of every global field.  kvset NULL with
+// NPRTRV = 1: the _m calls.
+extern "C" int emi_dist_spec_v(int kresol, int glob_space, const void *specg, int nfld_g, const int *kfrom, const int *kvset, const int *ksort, int loc_space,
+                               void *spec) {
+  return gs_m<true>(false, kresol, glob_space, specg, nfld_g, kfrom, kvset, ksort, 0, loc_space, spec, "DIST_SPEC", false);
+}
+extern "C" int emi_gath_spec_v(int kresol, int glob_space, void *specg, int nfld_g, const int *kto, const int *kvset, int loc_space, const void *spec) {
+  return gs_m<true>(true, kresol, glob_space, specg, nfld_g, kto, kvset, nullptr, 0, loc_space, spec, "GATH_SPEC", false);
+}
 
 template <class A>
 static int resolve_call(const char *who, const A *ap, A &a) {

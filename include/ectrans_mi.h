@@ -348,6 +348,8 @@ int emi_specnorm_partial(int kresol, int mem_space, const void *spec, int nfld, 
  *                 one after the other in field order: [n_mine][nspec2g] / [n_mine][ngptotg]  (= PGPG(ngptotg, n_mine))
  *   spec        : PSPEC(nfld, nspec2);   gp : PGP(nproma, nfld, ngpblks), elements past NGPTOT are left alone
  *   kfrom / kto : task (1-based) of every field; ksort (or NULL): field f lands in slot ksort[f] (1-based) of spec / gp
+ * With NPRTRV > 1 (the spherical four; the limited-area handles have no V-sets) the tasks are all NPROC = NPRTRW x NPRTRV, a grid
+ * field lives on every task's sub-band and emi_dist_spec / emi_gath_spec need the V-sets of the fields: emi_dist_spec_v / emi_gath_spec_v below.
  * With several tasks the host supplies two collectives over its tasks (an MPI or RCCL transport registers them, see
  * ectrans_amd/mpi and ectrans_amd/rccl): a broadcast and an all-gather-v of host bytes.                              */
 typedef int (*emi_bcast_fn)(void *user, void *buf, long long bytes, int root /* 0-based */);
@@ -366,7 +368,7 @@ int emi_edist_spec(int kresol, const void *specg, int nfld, const int *kfrom, co
 int emi_egath_spec(int kresol, void *specg, int nfld, const int *kto, const void *spec);
 int emi_edist_grid(int kresol, const void *gpg, int nfld, const int *kfrom, const int *ksort, int kproma, void *gp);
 int emi_egath_grid(int kresol, void *gpg, int nfld, const int *kto, int kproma, const void *gp);
-/* The same eight with a memory space per array: layouts, kfrom / kto / ksort, the handle checks and NPRTRV = 1 as above.
+/* The same eight with a memory space per array: layouts, kfrom / kto / ksort and the handle checks as above (V-sets: below).
  * glob_space, loc_space: EMI_MEM_HOST, EMI_MEM_DEVICE or EMI_MEM_AUTO (emi_ptr_space of that array); unlike the transforms the two
  * arrays of a call may live in different memories (a host I/O image beside device-resident fields).  The LOCAL array selects the path:
  *   host   : the routines above, unchanged (host collectives); a device global array beside it is EMI_ERR_ARG.
@@ -387,6 +389,20 @@ int emi_edist_spec_m(int kresol, int glob_space, const void *specg, int nfld, co
 int emi_egath_spec_m(int kresol, int glob_space, void *specg, int nfld, const int *kto, int loc_space, const void *spec);
 int emi_edist_grid_m(int kresol, int glob_space, const void *gpg, int nfld, const int *kfrom, const int *ksort, int kproma, int loc_space, void *gp);
 int emi_egath_grid_m(int kresol, int glob_space, void *gpg, int nfld, const int *kto, int kproma, int loc_space, const void *gp);
+/* V-sets (NPRTRV > 1) on the spherical eight.  Tasks are numbered over all NPROC = NPRTRW x NPRTRV of them, task t = w NPRTRV + v
+ * (1-based in kfrom / kto), and every collective above spans them all.
+ *   grid     : nothing new in the call.  Every task holds every field on its own points, with V-sets its sub-band of whole latitudes
+ *              ("ngptot", "nfrstlat" of the inquiries); global order is latitude order = task order; kproma blocks the sub-band.
+ *   spectral : kvset[nfld_g] names the V-set (1..NPRTRV) of every GLOBAL field.  Field j lives on the NPRTRW tasks of V-set kvset[j],
+ *              each with the wavenumbers of its W-set.  spec is PSPEC(nfl, nspec2) with the nfl fields of this task's own V-set,
+ *              ascending in j; nfl may be 0, and spec then NULL (pass loc_space explicitly; such a task follows the path of the others).
+ *              ksort is indexed by the local field and ranges over 1..nfl (dist_spec_control_mod.F90).  kfrom[j] / kto[j] may be any
+ *              task, also one outside V-set kvset[j]; specg holds the fields this task is source / target of, ascending, as above.
+ * kvset == NULL: with NPRTRV = 1 the _m calls; with NPRTRV > 1 "DIST_SPEC:KVSET MISSING, NPRTRV > 1" (GATH_SPEC likewise), which
+ * is also what emi_dist_spec / emi_gath_spec and their _m forms answer then.  A value outside 1..NPRTRV: "...:KVSET CONTAINS VALUES
+ * OUTSIDE RANGE".  With registered host collectives the tasks also compare a hash of kvset and fail together where it differs.      */
+int emi_dist_spec_v(int kresol, int glob_space, const void *specg, int nfld_g, const int *kfrom, const int *kvset, const int *ksort, int loc_space, void *spec);
+int emi_gath_spec_v(int kresol, int glob_space, void *specg, int nfld_g, const int *kto, const int *kvset, int loc_space, const void *spec);
 /* What emi_init was given (EMI_ERR_STATE before it): a Fortran host whose transport attached first (emi_mpi_attach,
  * emi_rccl_attach) learns its task number from here in SETUP_TRANS0.                                                 */
 int emi_inq_tasks(int *nproc, int *myproc);

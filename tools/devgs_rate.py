@@ -8,7 +8,14 @@ hipMemcpy of the bytes of the local array, in the same run, as the bandwidth yar
 (minimum) over windows of 20 calls (line 2: of one call) after a warm-up, a host clock around a window that ends in a device
 synchronise.  Nothing is asserted on the numbers; the results
 of the timed calls are compared with the host routine's bytes.  Run on the GPU:
-    python tools/devgs_rate.py [--calls 10] [--nfld 32] [--nsmax 639] [--out profiles/devgs_rate.txt]"""
+    python tools/devgs_rate.py [--calls 10] [--nfld 32] [--nsmax 639] [--out profiles/devgs_rate.txt]
+
+--nprtrw W --nprtrv V (several tasks): the tool starts itself W x V times over gloo, all tasks on cuda:0, and times GATH_SPEC and GATH_GRID
+of device-resident fields to a device image on task 1 (emi_gath_spec_v with the fields dealt round-robin to the V-sets; emi_gath_spec_m with
+V = 1).  Tasks that share one GPU over gloo measure the packing and the bookkeeping of the routines, not a device interconnect.  The
+gathered fields are compared with the bytes they were distributed from.  --lib PATH times another build of the library (an A/B run
+against an older commit; with V = 1 only entry points that it has are called).  Prints one line per routine; --out appends them.
+    python tools/devgs_rate.py --nprtrw 2 --nprtrv 2 --nsmax 159 [--lib other/libectrans_mi.so] [--out profiles/devgs_rate_vsets.txt]"""
 import argparse
 import ctypes as C
 import os
@@ -41,13 +48,101 @@ def timed(fn, calls, warm=2, inner=20):
     return statistics.median(ms), min(ms)
 
 
+def several_tasks(a):
+    """launch W x V copies of this tool (RANK in the environment marks a task) and pass on what task 1 printed"""
+    import socket
+    import subprocess
+    world = a.nprtrw * a.nprtrv
+    env = dict(os.environ, WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1")
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        env["MASTER_PORT"] = str(s.getsockname()[1])
+    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], env=dict(env, RANK=str(rank)), stdout=subprocess.PIPE,
+                              stderr=subprocess.STDOUT, text=True) for rank in range(world)]
+    outs = []
+    for p in procs:
+        try:
+            outs.append(p.communicate(timeout=a.timeout)[0])
+        except subprocess.TimeoutExpired:
+            for q in procs:
+                q.kill()
+            raise
+    for rank, (p, out) in enumerate(zip(procs, outs)):
+        if p.returncode != 0:
+            raise SystemExit("task %d failed:\n%s" % (rank + 1, out))
+    text = "".join(l + "\n" for l in outs[0].splitlines() if l.startswith("devgs_rate"))
+    print(text, end="")
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write(text)
+
+
+def one_task_of_several(a):
+    """GATH_SPEC and GATH_GRID of nfld device-resident fields to a device image on task 1, W x V tasks on cuda:0 over gloo"""
+    import torch.distributed as dist
+    rank, world, nf, n = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"]), a.nfld, a.nsmax
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    if a.lib:  # another build of the library, for an A/B run
+        et._L = et._bind(C.CDLL(os.path.abspath(a.lib)))
+        et._EMULATOR[0] = False
+    et.setup_trans0(kmax_resol=1, kprtrw=a.nprtrw, kprtrv=a.nprtrv, myproc=rank + 1, device=0)
+    nloen = np.array([20 + 4 * i for i in range(n + 1)] + [20 + 4 * i for i in reversed(range(n + 1))], dtype=np.int32)
+    r = et.setup_trans(n, len(nloen), nloen)
+    L = et.lib()
+    ns2g, ngg, ns2, ng = (et.trans_inq(r, k) for k in ("nspec2g", "ngptotg", "nspec2", "ngptot"))
+    one = np.ones(nf, dtype=np.int32)
+    kv = (np.arange(nf, dtype=np.int32) % a.nprtrv) + 1
+    nfl = int((kv == et.trans_inq(r, "mysetv")).sum())
+    ip = lambda x: x.ctypes.data_as(C.POINTER(C.c_int))
+    dp = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+    rng = np.random.default_rng(1)  # the same global fields on every task
+    spg, gpg = rng.uniform(-1.0, 1.0, (nf, ns2g)), rng.uniform(-1.0, 1.0, (nf, ngg))
+    dev = lambda x: torch.from_numpy(x).to("cuda:0")
+    first = rank == 0
+    sp_d, gp_d = torch.zeros((ns2, nfl), dtype=torch.float64, device="cuda:0"), torch.zeros((1, nf, ng), dtype=torch.float64, device="cuda:0")
+    in_s, in_g = (dev(spg), dev(gpg)) if first else (None, None)
+    out_s, out_g = (torch.zeros_like(in_s), torch.zeros_like(in_g)) if first else (None, None)
+    if a.nprtrv > 1:
+        dist_spec = lambda: L.emi_dist_spec_v(r, DEVICE, dp(in_s), nf, ip(one), ip(kv), None, DEVICE, dp(sp_d))
+        gath_spec = lambda: L.emi_gath_spec_v(r, DEVICE, dp(out_s), nf, ip(one), ip(kv), DEVICE, dp(sp_d))
+    else:
+        dist_spec = lambda: L.emi_dist_spec_m(r, DEVICE, dp(in_s), nf, ip(one), None, DEVICE, dp(sp_d))
+        gath_spec = lambda: L.emi_gath_spec_m(r, DEVICE, dp(out_s), nf, ip(one), DEVICE, dp(sp_d))
+    dist_grid = lambda: L.emi_dist_grid_m(r, DEVICE, dp(in_g), nf, ip(one), None, ng, DEVICE, dp(gp_d))
+    gath_grid = lambda: L.emi_gath_grid_m(r, DEVICE, dp(out_g), nf, ip(one), ng, DEVICE, dp(gp_d))
+
+    def ok(fn):
+        if fn() != 0:
+            raise SystemExit(L.emi_last_error().decode())
+
+    ok(dist_spec), ok(dist_grid)
+    what = "%d x %d tasks%s" % (a.nprtrw, a.nprtrv, (", library " + a.lib) if a.lib else "")
+    for name, fn, out, ref, mb in (("GATH_SPEC", gath_spec, out_s, spg, spg.nbytes / 1e6), ("GATH_GRID", gath_grid, out_g, gpg, gpg.nbytes / 1e6)):
+        dist.barrier()
+        med, mn = timed(lambda: ok(fn), a.calls, inner=5)
+        if first:
+            assert out.cpu().numpy().tobytes() == ref.tobytes(), name
+            print("devgs_rate %s, %s, O%d, %d fields, fp64, device image on task 1: %8.3f ms per call (minimum %8.3f), %7.2f GB/s of the %.1f MB of the fields"
+                  % (name, what, n + 1, nf, med, mn, mb / med, mb), flush=True)
+    et.trans_end()
+    dist.barrier()
+    dist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--nfld", type=int, default=32)
     ap.add_argument("--nsmax", type=int, default=639)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "devgs_rate.txt"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--nprtrw", type=int, default=1)
+    ap.add_argument("--nprtrv", type=int, default=1)
+    ap.add_argument("--lib", default=None)
+    ap.add_argument("--timeout", type=int, default=500)
     a = ap.parse_args()
+    if a.nprtrw * a.nprtrv > 1:
+        return one_task_of_several(a) if "RANK" in os.environ else several_tasks(a)
+    a.out = a.out or os.path.join(ROOT, "profiles", "devgs_rate.txt")
     nf, n = a.nfld, a.nsmax
     nloen = np.array([20 + 4 * i for i in range(n + 1)] + [20 + 4 * i for i in reversed(range(n + 1))], dtype=np.int32)
     et.setup_trans0(kmax_resol=1, device=0)
